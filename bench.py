@@ -16,6 +16,13 @@ B=64 utterances per GPU, T=1000 frames, U=100 labels, V=32, bigram FullNGram
 
 Run: python bench.py [--gpus N --steps K --warmup W]
      python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints one JSON line
+(value, ms_per_step, and the roofline figures of those same steps).
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
+--full adds the legs that take runs of their own after the timed steps: the
+B=256 north-star shape, realistic and cold weights, the JointWeightFn
+training step and the CPU baselines.
 """
 import argparse
 import json
@@ -81,7 +88,9 @@ def run_steps(W, nf, labels, nl, V, n, steps, warmup, dist_on, events=True, chec
   while the GPU's clock settles under the load (info['settle_calls'] counts
   them); fused:
   lt_loss_grad in one C-ABI call (fwd list; bwd list empty), else
-  lt_loss_forward (fwd list) + lt_loss_backward (bwd list)."""
+  lt_loss_forward (fwd list) + lt_loss_backward (bwd list).
+  info['outputs'] holds what the last timed step returned to its caller:
+  loss, log_z, num (the numerator's log-weight) and dW."""
   grad = torch.ones([W.shape[0]], dtype=torch.float32, device=W.device)
   ws = None
   if fused:
@@ -96,7 +105,7 @@ def run_steps(W, nf, labels, nl, V, n, steps, warmup, dist_on, events=True, chec
     if ev is not None:
       ev[0].record()
     if fused:
-      loss, _, _, dW = _native.loss_grad(W, nf, labels, nl, V, n, False, workspace=ws)
+      loss, log_z, num, dW = _native.loss_grad(W, nf, labels, nl, V, n, False, workspace=ws)
       if ev is not None:
         ev[1].record()
     else:
@@ -110,7 +119,7 @@ def run_steps(W, nf, labels, nl, V, n, steps, warmup, dist_on, events=True, chec
       ev[2].record()
     if dist_on:
       bucket.all_reduce_step(loss)
-    return dW
+    return loss, log_z, num, dW
 
   # the shader clock under this load rises from ~2.2 to ~2.39 GHz over the
   # first 25-50 calls after an idle GPU (a probe beside the calls,
@@ -142,8 +151,12 @@ def run_steps(W, nf, labels, nl, V, n, steps, warmup, dist_on, events=True, chec
   t0 = time.perf_counter()
   if whole:
     ew[0].record()
+  last = None
   for i in range(steps):
-    step(evs[i])
+    # the previous step's outputs go back to the allocator before the call,
+    # as when they are dropped: every step writes the same buffers
+    last = None
+    last = step(evs[i])
   if whole:
     ew[1].record()
   torch.cuda.synchronize()
@@ -151,6 +164,8 @@ def run_steps(W, nf, labels, nl, V, n, steps, warmup, dist_on, events=True, chec
     torch.distributed.barrier()
   torch.cuda.synchronize()
   wall = time.perf_counter() - t0
+  if info is not None and last is not None:
+    info['outputs'] = dict(zip(('loss', 'log_z', 'num', 'dW'), last))
   if whole:
     fwd_ms = [ew[0].elapsed_time(ew[1]) / steps] * steps
   else:
@@ -429,6 +444,28 @@ def loss_grad_design(B, T, U, V, n, C, device):
       algorithmic_bytes(T, U, V, C, checkpoints=False)[:2])
 
 
+DUMP_BUDGET_BYTES = 48 * 1000 * 1000  # of the 64 MB a dump may take in all
+
+
+def dump_outputs(outputs, out_dir, seed=4321):
+  """--dump-outputs: the arrays the last timed step returned, one
+  DIR/<name>.npy each, float32. An array of at most 1 MB is written whole
+  (loss, log_z, num); of a larger one (dW at the bench shape is 279 MB) a
+  fixed sample if it exceeds its share of the budget: the elements at flat
+  indices drawn once from a seeded host generator, sorted, the same for
+  every run with the same shapes."""
+  os.makedirs(out_dir, exist_ok=True)
+  large = sum(1 for x in outputs.values() if x.numel() > 250000)
+  share = DUMP_BUDGET_BYTES // (4 * max(large, 1))
+  for name, x in outputs.items():
+    x = x.detach().float()
+    if x.numel() > share:
+      g = torch.Generator().manual_seed(seed)
+      idx = torch.randint(0, x.numel(), [share], generator=g).sort().values
+      x = x.reshape(-1)[idx.to(x.device)]
+    np.save(os.path.join(out_dir, f'{name}.npy'), x.cpu().numpy())
+
+
 def launch_ranks(argv, n):
   """`--gpus N > 1` without a torch.distributed environment: start N ranks
   with torch.distributed.run as a CHILD process (one process per GPU, RCCL
@@ -546,6 +583,14 @@ def main():
   ap.add_argument('--cpu-ref-utts', type=int,
                   default=int(os.environ.get('LT_BENCH_CPU_REF_UTTS', 8)),
                   help='utterances of the PyTorch-CPU cpu_ref baseline (0: skip)')
+  ap.add_argument('--full', action='store_true',
+                  help='after the timed steps also measure the legs that take runs of their own: '
+                       'the B=256 north-star shape, realistic / cold weights, the JointWeightFn '
+                       'training step and the CPU baselines (the --no-* and --cpu-* options '
+                       'below choose among them)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write what the last timed step returned (loss, log_z, num, dW; a fixed '
+                       'seeded sample of a large array) as DIR/<name>.npy, float32')
   ap.add_argument('--no-north-star', action='store_true')
   ap.add_argument('--no-joint', action='store_true')
   ap.add_argument('--no-weights', action='store_true',
@@ -609,6 +654,10 @@ def main():
   wall, fwd_ms, bwd_ms, calls = run_steps(W, nf, labels, nl, V, n, args.steps, args.warmup,
                                           dist_on, checkpoints=ckpt, fused=fused,
                                           settle_s=args.settle_ms * 1e-3, info=settle)
+  outputs = settle.pop('outputs', None)
+  if args.dump_outputs and rank == 0:
+    dump_outputs(outputs, args.dump_outputs)
+  del outputs
 
   t = torch.tensor([wall], dtype=torch.float64, device=device)
   if dist_on:
@@ -687,8 +736,10 @@ def main():
     result['step_gbs'] = survey_b * int(nf_g.sum()) / (wall / args.steps) / 1e9
     result['hbm_frac_step'] = result['step_gbs'] / HBM_PEAK_GBS
 
+  # --full: the legs below take runs of their own; a plain run ends with the
+  # line of its timed steps
   # north-star shape (B=256 on one GPU), measured in the same run at N=1
-  if not dist_on and not args.no_north_star and B != 256:
+  if args.full and not dist_on and not args.no_north_star and B != 256:
     del W
     torch.cuda.empty_cache()
     W2, nf2, lab2, nl2 = make_inputs(256, T, U, V, C, device, seed=99)
@@ -715,13 +766,13 @@ def main():
     if not args.no_joint:
       result['joint_weight_fn_step'] = joint_step_leg(T, U, V, n, device)
 
-  if rank == 0 and args.cpu_twin_utts > 0:
+  if args.full and rank == 0 and args.cpu_twin_utts > 0:
     # the C++ host twin beside every line, N > 1 included (rank 0, after the
     # timed steps, so the other ranks only wait at the final barrier): at
     # N > 1 a shorter sample (about 5 s), the same cells/s measure
     result['cpu_baseline'] = cpu_twin(T, U, V, n, C, args.cpu_twin_utts,
                                       min_seconds=10.0 if not dist_on else 5.0)
-  if rank == 0 and not dist_on:
+  if args.full and rank == 0 and not dist_on:
     if args.cpu_ref_utts > 0:
       result['cpu_baseline_torch'] = cpu_ref(T, U, V, n, args.cpu_ref_utts)
     if args.cpu_utts > 0:

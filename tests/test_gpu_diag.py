@@ -21,8 +21,7 @@ DIAG = os.path.join(ROOT, 'build', 'diag', 'liblt_lattice_diag.so')
 
 
 def test_chunk_handoff_timeout_route(cuda):
-  if not os.path.exists(DIAG):
-    pytest.skip('diagnostic build absent (make diag)')
+  assert os.path.exists(DIAG), 'diagnostic build absent (build() makes it: make diag)'
   env = dict(os.environ, LT_LIB_PATH=DIAG, LT_CK_DBG='512')
   r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'diag_timeout_child.py')],
                      cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)
@@ -33,8 +32,7 @@ def test_chunk_handoff_timeout_route(cuda):
 def test_quad_trigram_recursions(cuda):
   """The quad trigram recursions (lt_tri4.hip; diagnostic build only, they
   measured slower than the one-workgroup kernel) still match the oracle."""
-  if not os.path.exists(DIAG):
-    pytest.skip('diagnostic build absent (make diag)')
+  assert os.path.exists(DIAG), 'diagnostic build absent (build() makes it: make diag)'
   env = dict(os.environ, LT_LIB_PATH=DIAG, LT_TRI4='1')
   r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'diag_tri4_child.py')],
                      cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)

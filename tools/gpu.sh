@@ -11,7 +11,7 @@
 #   tests      GPU suite (the full-size file apart, verbosely), then smoke()
 #   full       the full-size file alone
 #   k=EXPR     pytest -m gpu -k EXPR (e.g. k=cfg4)
-#   bench      bench.py at the driver's flags (--warmup 5 --steps 20) and at its defaults
+#   bench      bench.py --full at the driver's flags (--warmup 5 --steps 20) and at its defaults
 #   trace      rocprofv3 --kernel-trace --stats: the bench call, B=256, cfg4 Viterbi, cfg5 trigram
 #   pmc        SQ counter passes of the bench call, cfg4 and cfg5; FETCH_SIZE / WRITE_SIZE of
 #              the bench call (tools/chunk_prof.py) and of B=256
@@ -54,13 +54,13 @@ for step in "$@"; do
     full) t_run full.log 500 tests/test_gpu_full_size.py -v ;;
     k=*) t_run k_$(echo "${step#k=}" | tr -c 'A-Za-z0-9_\n' _).log 500 tests -m gpu -v -k "${step#k=}" ;;
     bench)
-      timeout -k 10 400 python -u bench.py --warmup 5 --steps 20 > $out/bench_driver_flags.json \
-        2> $out/bench_driver_flags.err || exit $?
-      timeout -k 10 400 python -u bench.py > $out/bench.json 2> $out/bench.err || exit $?
+      timeout -k 10 400 python -u bench.py --full --warmup 5 --steps 20 \
+        > $out/bench_driver_flags.json 2> $out/bench_driver_flags.err || exit $?
+      timeout -k 10 400 python -u bench.py --full > $out/bench.json 2> $out/bench.err || exit $?
       ;;
     trace)
       timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/ktb -o run -- python bench.py \
-        --steps 20 --warmup 5 --no-joint --no-weights --cpu-utts 0 --cpu-ref-utts 0 \
+        --full --steps 20 --warmup 5 --no-joint --no-weights --cpu-utts 0 --cpu-ref-utts 0 \
         --cpu-twin-utts 0 > $out/ktb.log 2>&1 || exit $?
       BS=256 N=10 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/kt256 -o run -- \
         python tools/time_call.py > $out/kt256.log 2>&1 || exit $?
