@@ -480,4 +480,8 @@ const char* lt_version(void);
 }
 #endif
 
+/* Forced alignment of label strings (the same library; its two entry points
+ * and their documentation live in a header of their own). */
+#include "lt_align.h"
+
 #endif /* LT_LATTICE_H_ */

@@ -91,6 +91,8 @@ _SIG = {
     'lt_table_num_backward': [_G, _TP, _I32] + [_P] * 8 + [ctypes.c_size_t, _P],
     'lt_table_viterbi_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_viterbi': [_G, _TP, _P, _P, _I32, _P, _P, _P, ctypes.c_size_t, _P],
+    'lt_table_align_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
+    'lt_table_align': [_G, _TP] + [_P] * 8 + [ctypes.c_size_t, _P],
     'lt_joint_weights_workspace_bytes': [ctypes.c_int64, _I32, _I32,
                                          ctypes.POINTER(ctypes.c_size_t)],
     'lt_joint_weights': [ctypes.c_int64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P,
@@ -114,7 +116,10 @@ _SIG = {
     'lt_viterbi': [ctypes.POINTER(Problem), _P, _P, _I32, _P, _P, _P, _P, _P, ctypes.c_size_t,
                    _P],
 }
-EXPORTED = tuple(_SIG) + ('lt_last_error', 'lt_version')
+# the functions each header of the C ABI declares: include/lt_align.h (forced
+# alignment) and include/lt_lattice.h (everything else)
+EXPORTED_ALIGN = ('lt_table_align_workspace_bytes', 'lt_table_align')
+EXPORTED = tuple(n for n in _SIG if n not in EXPORTED_ALIGN) + ('lt_last_error', 'lt_version')
 
 
 def lib():
@@ -613,6 +618,44 @@ def table_viterbi(graph, W, num_frames, label_convention):
                                 _ptr(num_frames), label_convention, _ptr(labels), _ptr(weight),
                                 _ptr(ws), nbytes.value, _stream()), 'lt_table_viterbi')
   return labels, weight
+
+
+LT_EUNSUPPORTED = -2
+
+
+def table_align_supported(graph, W, labels):
+  """Whether lt_table_align takes this problem (U <= 255, K <= 15): a
+  host-only query, no launch. Other errors raise."""
+  pb = _tproblem(graph, W, labels.shape[-1])
+  nbytes = ctypes.c_size_t(0)
+  rc = lib().lt_table_align_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
+                                            ctypes.byref(nbytes))
+  if rc == LT_EUNSUPPORTED:
+    return False
+  _check(rc, 'lt_table_align_workspace_bytes')
+  return True
+
+
+def table_align(graph, W, num_frames, labels, num_labels):
+  """lt_table_align: forced alignment of the label strings, one launch.
+  Returns (alignment_labels int64 [B, T*A], label_frames int64 [B, U], path
+  weights [B]); raises LatticeLibraryError (LT_EUNSUPPORTED) past U = 255 or
+  K = 15."""
+  pb = _tproblem(graph, W, labels.shape[-1])
+  B, T = W.shape[:2]
+  U = labels.shape[-1]
+  nbytes = ctypes.c_size_t(0)
+  _check(lib().lt_table_align_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
+                                              ctypes.byref(nbytes)),
+         'lt_table_align_workspace_bytes')
+  ws = (torch.empty([nbytes.value], dtype=torch.uint8, device=W.device) if nbytes.value else None)
+  out = torch.empty([B, T * graph.num_alignment_states()], dtype=torch.int64, device=W.device)
+  frames = torch.empty([B, U], dtype=torch.int64, device=W.device)
+  weight = _f32([B], W)
+  _check(lib().lt_table_align(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W), _ptr(num_frames),
+                              _ptr(labels), _ptr(num_labels), _ptr(out), _ptr(frames),
+                              _ptr(weight), _ptr(ws), nbytes.value, _stream()), 'lt_table_align')
+  return out, frames, weight
 
 
 JOINT_BF16, JOINT_SPLIT = 0, 1  # lt_joint_weights_ex precisions (include/lt_lattice.h)

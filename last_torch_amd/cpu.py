@@ -27,6 +27,9 @@ MaxTropical's first-argmax rule prefers the blank, then fewer expansions.
   viterbi       lattices.py:185-247   max-tropical distance, labels from its
                                       derivative w.r.t. one zero lexical mask
                                       per expansion
+  align         (not in the reference) forced alignment: the max-tropical
+                                      string distance differentiated w.r.t.
+                                      the string's lexical weights
 """
 import torch
 
@@ -110,10 +113,17 @@ def num_forward(W: torch.Tensor, nf: torch.Tensor, labels: torch.Tensor, nl: tor
   """Shortest distance of the lattice intersected with the label string
   (lattices.py:250-377): alpha over string positions 0..U, read at nl. The
   lexical step on the string moves every position one place up."""
-  K = expansions(alignment)
-  B, T = W.shape[:2]
-  U = labels.shape[-1]
   blank, lex = string_weights(W, labels, context)
+  return _string_distance(blank, lex, nf, nl, expansions(alignment), semiring)
+
+
+def _string_distance(blank: torch.Tensor, lex: torch.Tensor, nf: torch.Tensor, nl: torch.Tensor,
+                     K: int, semiring) -> torch.Tensor:
+  """num_forward's recursion over the string's own weights (string_weights):
+  blank [B, T, U+1], lex [B, T, U]."""
+  W = blank
+  B, T = blank.shape[:2]
+  U = lex.shape[-1]
   zero = semiring.zeros([B, 1], W.dtype)
   one = semiring.ones([], W.dtype)
   alpha = torch.where(torch.arange(U + 1) == 0, one, semiring.zeros([], W.dtype)).expand(B, U + 1)
@@ -174,3 +184,39 @@ def viterbi(W: torch.Tensor, nf: torch.Tensor, context: contexts.ContextDependen
   if K:
     slots.append(torch.zeros_like(slots[0]))
   return torch.stack(slots, dim=-1).reshape(B, T * len(slots)), dist.detach()
+
+
+def align(W: torch.Tensor, nf: torch.Tensor, labels: torch.Tensor, nl: torch.Tensor,
+          context: contexts.ContextDependency, alignment):
+  """Forced alignment: the max-tropical string distance differentiated with
+  respect to the string's own per-frame lexical weights (string_weights), in
+  viterbi's style: the one-hot derivative at (t, u) says the arc leaving
+  string position u is taken on frame t (first-argmax ties: the blank, then
+  fewer expansions). Returns (alignment_labels [B, T * A], label_frames
+  [B, U], path_weights [B]): slot i of frame t holds the true label (0 for an
+  epsilon) of the frame's (i+1)-th lexical arc, else 0; label_frames is -1
+  from num_labels on. Utterances of distance -inf are unaligned: all 0 / -1."""
+  K = expansions(alignment)
+  B, T = W.shape[:2]
+  U = labels.shape[-1]
+  V = W.shape[-1] - 1
+  A = K + 1 if K else 1
+  lab = labels.long()
+  with torch.enable_grad():
+    blank, lex = string_weights(W.detach(), lab, context)
+    lex = lex.detach().requires_grad_(True)
+    dist = _string_distance(blank, lex, nf, nl, K, semirings.MaxTropical)
+    grad = (torch.autograd.grad(dist.sum(), [lex], allow_unused=True)[0]
+            if dist.requires_grad else None)
+  dist = dist.detach()
+  taken = torch.zeros([B, T, U], dtype=torch.bool) if grad is None else grad > 0
+  taken = taken & (dist > -torch.inf)[:, None, None]
+  label_frames = torch.where(taken.any(dim=1), taken.int().argmax(dim=1),
+                             torch.full([B, U], -1)).long()
+  # the frame's lexical arcs are consecutive positions: their rank is the slot
+  true = torch.where((lab >= 1) & (lab <= V), lab, torch.zeros_like(lab))
+  slot = torch.cumsum(taken.long(), dim=2) - 1
+  out = torch.zeros([B, T, A], dtype=torch.long)
+  b, t, u = torch.nonzero(taken, as_tuple=True)
+  out[b, t, slot[b, t, u]] = true[b, u]
+  return out.reshape(B, T * A), label_frames, dist

@@ -16,6 +16,8 @@ weights once through the ``WeightFn`` plugin as a contiguous
   _string_forward -> lt_num_forward; autograd: lt_loss_backward (Log) /
                      lt_table_num_backward (MaxTropical, Real)
   shortest_path   -> lt_viterbi
+  align           -> lt_table_align (forced alignment; not in the reference);
+                     past its range lt_table_num_backward (Max) compacted
 
 The device of the arc weights picks the implementation, as in the
 reference: ROCm tensors run the HIP kernels (FrameDependent and
@@ -466,6 +468,78 @@ class RecognitionLattice(nn.Module, Generic[T]):
     labels = self._home(labels.reshape(*batch_dims, -1), frames)
     num_alignment_labels = self.alignment.num_states() * num_frames
     return labels, num_alignment_labels, self._home(weights.reshape(batch_dims), frames)
+
+  def align(self, frames: torch.Tensor, num_frames: torch.Tensor, labels: torch.Tensor,
+            num_labels: torch.Tensor, cache: Optional[T] = None):
+    """Forced alignment (not in the reference): the MaxTropical best path of
+    the lattice intersected with the label string, i.e. on which frame each
+    label is emitted. Ties: the blank term wins (FrameDependent), the fewest
+    expansions win (FrameLabelDependent); labels outside 1..V are epsilons.
+
+    Returns (alignment_labels [batch..., T*A], label_frames [batch..., U],
+    path_weights [batch...]), A = alignment.num_states(): slot i of frame t
+    holds the true label y of the (i+1)-th lexical arc the path takes in that
+    frame (0 for an epsilon), else 0 -- shortest_path's slot layout, without a
+    label convention (D5 is not reproduced); label_frames[u] is the frame on
+    which the arc leaving string position u is taken, -1 for u >= num_labels;
+    path_weights equals _string_forward(..., MaxTropical) bit for bit. An
+    utterance of weight -inf (no path, -inf arcs, num_labels outside [0, U])
+    is unaligned: all 0 / all -1.
+    """
+    batch_dims = tuple(num_frames.shape)
+    if tuple(frames.shape[:-2]) != batch_dims:
+      raise ValueError('frames and num_frames have different batch_dims: '
+                       f'{tuple(frames.shape[:-2])} vs {batch_dims}')
+    if tuple(labels.shape[:-1]) != batch_dims:
+      raise ValueError('labels and num_frames have different batch_dims: '
+                       f'{tuple(labels.shape[:-1])} vs {batch_dims}')
+    if tuple(num_labels.shape) != batch_dims:
+      raise ValueError('num_labels and num_frames have different batch_dims: '
+                       f'{tuple(num_labels.shape)} vs {batch_dims}')
+    W, nf, batch_dims, B, _, _, _ = self._prepare(cache, frames, num_frames)
+    lab = torch.as_tensor(labels).reshape(B, -1).to(device=W.device, dtype=torch.int32).contiguous()
+    nl = _lengths(num_labels, B, W.device)
+    with torch.no_grad():
+      W = W.detach()
+      if W.device.type == 'cpu':
+        out = cpu.align(W, nf, lab, nl.long(), self.context, self.alignment)
+      else:
+        graph = self._graph(W.device)
+        # one launch (lt_table_align); past its range (U > 255, K > 15) the
+        # dense string gradient, compacted
+        if _native.table_align_supported(graph, W, lab):
+          out = _native.table_align(graph, W, nf, lab, nl)
+        else:
+          out = self._align_dense(graph, W, nf, lab, nl)
+    alignment_labels, label_frames, weights = out
+    return (self._home(alignment_labels.reshape(*batch_dims, -1), frames),
+            self._home(label_frames.reshape(*batch_dims, -1), frames),
+            self._home(weights.reshape(batch_dims), frames))
+
+  @staticmethod
+  def _align_dense(graph, W, nf, lab, nl):
+    """align through the dense one-hot string gradient
+    (lt_table_num_backward in MaxTropical, [B, T, C, V+1]) and a torch
+    compaction: a frame's lexical arcs are the next `count` string positions,
+    count = the sum of its lexical gradients."""
+    num, dW = _native.table_num_backward(graph, W, nf, lab, nl, _native.SEMIRING_MAX)
+    B, T = W.shape[:2]
+    U = lab.shape[-1]
+    A = graph.num_alignment_states()
+    aligned = num > -torch.inf
+    count = dW[..., 1:].float().sum(dim=(2, 3)).round().long() * aligned[:, None]  # [B, T]
+    end = torch.cumsum(count, dim=1)
+    start = end - count
+    pos = torch.arange(U, device=W.device).expand(B, U).contiguous()
+    frame = torch.searchsorted(end.contiguous(), pos, right=True)
+    label_frames = torch.where(frame < T, frame, torch.full_like(frame, -1))
+    true = torch.where((lab >= 1) & (lab <= graph.V), lab, torch.zeros_like(lab)).long()
+    slot = torch.arange(A, device=W.device)
+    idx = start[:, :, None] + slot                                      # [B, T, A]
+    padded = torch.cat([true, true.new_zeros([B, 1])], dim=1)
+    picked = torch.gather(padded, 1, idx.clamp(max=U).reshape(B, T * A)).reshape(B, T, A)
+    alignment_labels = torch.where(slot < count[:, :, None], picked, torch.zeros_like(picked))
+    return alignment_labels.reshape(B, T * A), label_frames, num
 
   def _string_forward(self, cache: T, frames: torch.Tensor, num_frames: torch.Tensor,
                       labels: torch.Tensor, num_labels: torch.Tensor,
