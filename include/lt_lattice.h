@@ -483,5 +483,7 @@ const char* lt_version(void);
 /* Forced alignment of label strings (the same library; its two entry points
  * and their documentation live in a header of their own). */
 #include "lt_align.h"
+/* Sampling alignment paths from the lattice posterior, likewise. */
+#include "lt_sample.h"
 
 #endif /* LT_LATTICE_H_ */

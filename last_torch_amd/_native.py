@@ -93,6 +93,9 @@ _SIG = {
     'lt_table_viterbi': [_G, _TP, _P, _P, _I32, _P, _P, _P, ctypes.c_size_t, _P],
     'lt_table_align_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_align': [_G, _TP] + [_P] * 8 + [ctypes.c_size_t, _P],
+    'lt_table_sample_workspace_bytes': [_G, _TP, _I32, ctypes.POINTER(ctypes.c_size_t)],
+    'lt_table_sample': [_G, _TP, _P, _P, _P, _P, _I32, ctypes.c_uint64, _P, _P, _P,
+                        ctypes.c_size_t, _P],
     'lt_joint_weights_workspace_bytes': [ctypes.c_int64, _I32, _I32,
                                          ctypes.POINTER(ctypes.c_size_t)],
     'lt_joint_weights': [ctypes.c_int64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P,
@@ -117,9 +120,12 @@ _SIG = {
                    _P],
 }
 # the functions each header of the C ABI declares: include/lt_align.h (forced
-# alignment) and include/lt_lattice.h (everything else)
+# alignment), include/lt_sample.h (path sampling) and include/lt_lattice.h
+# (everything else)
 EXPORTED_ALIGN = ('lt_table_align_workspace_bytes', 'lt_table_align')
-EXPORTED = tuple(n for n in _SIG if n not in EXPORTED_ALIGN) + ('lt_last_error', 'lt_version')
+EXPORTED_SAMPLE = ('lt_table_sample_workspace_bytes', 'lt_table_sample')
+EXPORTED = (tuple(n for n in _SIG if n not in EXPORTED_ALIGN + EXPORTED_SAMPLE) +
+            ('lt_last_error', 'lt_version'))
 
 
 def lib():
@@ -656,6 +662,34 @@ def table_align(graph, W, num_frames, labels, num_labels):
                               _ptr(labels), _ptr(num_labels), _ptr(out), _ptr(frames),
                               _ptr(weight), _ptr(ws), nbytes.value, _stream()), 'lt_table_align')
   return out, frames, weight
+
+
+def table_sample(graph, W, num_frames, log_z, alpha, num_samples, seed):
+  """lt_table_sample: num_samples paths per utterance from the lattice
+  posterior, one launch. log_z [B] and alpha [B, T, C] are table_forward's or
+  den_forward's in SEMIRING_LOG. Returns (labels int64 [B, S, T], path weights
+  [B, S]); raises LatticeLibraryError (LT_EUNSUPPORTED) for
+  FrameLabelDependent graphs."""
+  pb = _tproblem(graph, W)
+  B, T = W.shape[:2]
+  S = int(num_samples)
+  nbytes = ctypes.c_size_t(0)
+  _check(lib().lt_table_sample_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb), S,
+                                               ctypes.byref(nbytes)),
+         'lt_table_sample_workspace_bytes')
+  ws = (torch.empty([nbytes.value], dtype=torch.uint8, device=W.device) if nbytes.value else None)
+  log_z = log_z.to(torch.float32).contiguous()
+  alpha = alpha.to(torch.float32).contiguous()
+  if tuple(alpha.shape) != (B, T, graph.C) or tuple(log_z.shape) != (B,):
+    raise ValueError(f'alpha {tuple(alpha.shape)} / log_z {tuple(log_z.shape)} do not match '
+                     f'[{B}, {T}, {graph.C}] / [{B}]')
+  labels = torch.empty([B, S, T], dtype=torch.int64, device=W.device)
+  weight = _f32([B, S], W)
+  _check(lib().lt_table_sample(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W), _ptr(num_frames),
+                               _ptr(log_z), _ptr(alpha), S, int(seed) & 0xffffffffffffffff,
+                               _ptr(labels), _ptr(weight), _ptr(ws), nbytes.value, _stream()),
+         'lt_table_sample')
+  return labels, weight
 
 
 JOINT_BF16, JOINT_SPLIT = 0, 1  # lt_joint_weights_ex precisions (include/lt_lattice.h)

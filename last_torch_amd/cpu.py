@@ -30,6 +30,9 @@ MaxTropical's first-argmax rule prefers the blank, then fewer expansions.
   align         (not in the reference) forced alignment: the max-tropical
                                       string distance differentiated w.r.t.
                                       the string's lexical weights
+  sample        (not in the reference) paths from the posterior exp(w) / Z:
+                                      Gumbel-max on Philox4x32-10, walked
+                                      backwards over alpha (lt_sample.h)
 """
 import torch
 
@@ -220,3 +223,144 @@ def align(W: torch.Tensor, nf: torch.Tensor, labels: torch.Tensor, nl: torch.Ten
   b, t, u = torch.nonzero(taken, as_tuple=True)
   out[b, t, slot[b, t, u]] = true[b, u]
   return out.reshape(B, T * A), label_frames, dist
+
+
+# ---------------------------------------------------------------------------
+# Sampling paths from the lattice posterior (include/lt_sample.h)
+# ---------------------------------------------------------------------------
+_M32 = 0xffffffff
+
+
+def _mulhilo(m: int, c: torch.Tensor):
+  """(high, low) 32-bit words of m * c for int64 tensors holding 32-bit
+  values: the high word from 16-bit halves of c (no product passes 2^49),
+  the low word from the wrapping int64 product."""
+  hi = (m * (c >> 16) + ((m * (c & 0xffff)) >> 16)) >> 16
+  return hi, (m * c) & _M32
+
+
+def philox4x32(counter, key):
+  """Philox4x32-10 (Random123's constants and round function) on int64
+  tensors of 32-bit words: counter = (c0, c1, c2, c3), key = (k0, k1), any
+  broadcastable shapes. Returns the four output words."""
+  c0, c1, c2, c3 = counter
+  k0, k1 = key
+  for _ in range(10):
+    hi0, lo0 = _mulhilo(0xD2511F53, c0)
+    hi1, lo1 = _mulhilo(0xCD9E8D57, c2)
+    c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+    k0 = (k0 + 0x9E3779B9) & _M32
+    k1 = (k1 + 0xBB67AE85) & _M32
+  return c0, c1, c2, c3
+
+
+def sample_noise(seed: int, b, s, t, k) -> torch.Tensor:
+  """g(b, s, t, p, y) of include/lt_sample.h for k = p*(V+1) + y (int64
+  tensors, broadcastable): -log(-log u), u = ((r >> 8) + 0.5) 2^-24, in fp32.
+  u is an fp32 number while r >> 8 < 2^23; above that 1 - u is one, and
+  -log u = -log1p(-(1 - u))."""
+  k = torch.as_tensor(k)
+  dev = k.device
+  seed = int(seed) & 0xffffffffffffffff
+  key = (torch.tensor(seed & _M32, device=dev), torch.tensor(seed >> 32, device=dev))
+  shape = torch.broadcast_shapes(*(tuple(torch.as_tensor(x).shape) for x in (b, s, t, k)))
+  ctr = [torch.as_tensor(x, device=dev).to(torch.int64).expand(shape) for x in (k >> 2, t, s, b)]
+  out = philox4x32(ctr, key)
+  sel = (k & 3).expand(shape)
+  r = torch.where(sel < 2, torch.where(sel == 0, out[0], out[1]),
+                  torch.where(sel == 2, out[2], out[3]))
+  x = r >> 8
+  low = -torch.log((x.float() + 0.5) * 2.0**-24)
+  high = -torch.log1p(-(((1 << 25) - 2 * x - 1).float() * 2.0**-25))
+  return -torch.log(torch.where(x < (1 << 23), low, high))
+
+
+def _pick(score: torch.Tensor, k: torch.Tensor):
+  """Index along the last dim of the largest score, ties to the smallest k;
+  NaN scores never win (all NaN: the smallest k)."""
+  score = torch.where(torch.isnan(score), torch.full_like(score, -torch.inf), score)
+  best = score.max(dim=-1, keepdim=True).values
+  big = torch.iinfo(torch.int64).max
+  return torch.where(score == best, k, torch.full_like(k, big)).argmin(dim=-1)
+
+
+def _in_arc_table(table: torch.Tensor):
+  """The arcs into each state, padded: (k [C, D], p [C, D], valid [C, D]),
+  candidate 0 the blank arc (q, 0), then the in-arcs (p, y) with
+  table[p, y-1] = q; k = p*(V+1) + y."""
+  C, V = table.shape
+  dst = table.reshape(-1).long()
+  order = torch.argsort(dst, stable=True)
+  deg = torch.bincount(dst, minlength=C)
+  D = int(deg.max()) + 1
+  start = torch.cumsum(deg, 0) - deg
+  rank = torch.arange(C * V, device=table.device) - start[dst[order]]
+  p = order // V
+  k = p * (V + 1) + order % V + 1
+  q = torch.arange(C, device=table.device)
+  ck = torch.zeros([C, D], dtype=torch.int64, device=table.device)
+  cp = torch.zeros_like(ck)
+  ok = torch.zeros([C, D], dtype=torch.bool, device=table.device)
+  ck[:, 0], cp[:, 0], ok[:, 0] = q * (V + 1), q, True
+  ck[dst[order], rank + 1] = k
+  cp[dst[order], rank + 1] = p
+  ok[dst[order], rank + 1] = True
+  return ck, cp, ok
+
+
+def sample(W: torch.Tensor, nf: torch.Tensor, context: contexts.ContextDependency,
+           num_samples: int, seed: int, log_z: torch.Tensor = None, alpha: torch.Tensor = None):
+  """num_samples paths per utterance from p(pi) = exp(w(pi)) / Z of the
+  denominator lattice x FrameDependent, by the definition of
+  include/lt_sample.h (Gumbel-max on Philox4x32-10, walked backwards over
+  alpha) in torch ops: one step per frame, vectorised over utterances,
+  samples and candidate arcs. Device-agnostic when log_z [B] and alpha
+  [B, T, C] (the Log forward's) are given; else they come from den_forward.
+  Returns (labels int64 [B, S, T], path weights [B, S], log_z [B])."""
+  if not hasattr(context, 'next_state_table'):
+    raise NotImplementedError(f'{type(context).__name__} has no next-state table')
+  table = context.next_state_table
+  table = torch.as_tensor(table() if callable(table) else table).to(W.device)
+  if log_z is None or alpha is None:
+    log_z, alpha = den_forward(W, nf, context, alignments.FrameDependent(), semirings.Log)
+  W = W.float()
+  alpha = alpha.float()
+  dev = W.device
+  B, T, C, R = W.shape
+  S = int(num_samples)
+  nf = nf.to(dev).long().clamp(0, T)
+  nf_host = nf.tolist()
+  sampled = torch.isfinite(log_z.to(dev))
+  ck, cp, ok = _in_arc_table(table)
+  bb = torch.arange(B, device=dev)[:, None, None]
+  ss = torch.arange(S, device=dev)[None, :, None]
+  all_k = torch.arange(C * R, device=dev)
+  labels = torch.zeros([B, S, T], dtype=torch.int64, device=dev)
+  weight = torch.zeros([B, S], dtype=torch.float32, device=dev)
+  q = torch.zeros([B, S], dtype=torch.int64, device=dev)
+  neg = torch.tensor(-torch.inf, device=dev)
+  for t in range(max(nf_host, default=0) - 1, -1, -1):
+    Wt = W[:, t].reshape(B, C * R)
+    # the arcs into q (frames before the last live one)
+    k, p, valid = ck[q], cp[q], ok[q]                               # [B, S, D]
+    a = torch.gather(alpha[:, t], 1, p.reshape(B, -1)).reshape(p.shape)
+    w = torch.gather(Wt, 1, k.reshape(B, -1)).reshape(k.shape)
+    score = torch.where(valid, (a + w) + sample_noise(seed, bb, ss, t, k), neg)
+    j = _pick(score, torch.where(valid, k, torch.full_like(k, C * R)))[..., None]
+    kw, pw, ww = (torch.gather(x, 2, j)[..., 0] for x in (k, p, w))
+    last = [b for b in range(B) if nf_host[b] - 1 == t]
+    if last:  # the last live frame: every arc of the frame
+      lb = torch.tensor(last, device=dev)
+      kk = all_k.expand(len(last), S, C * R)
+      al = alpha[lb, t][:, None, all_k // R]
+      wl = Wt[lb][:, None, :].expand(len(last), S, C * R)
+      sc = (al + wl) + sample_noise(seed, lb[:, None, None], ss, t, kk)
+      jl = _pick(sc, kk)
+      kw[lb], pw[lb], ww[lb] = jl, jl // R, torch.gather(wl, 2, jl[..., None])[..., 0]
+    live = (t < nf)[:, None]
+    labels[:, :, t] = torch.where(live, kw - pw * R, labels[:, :, t])
+    weight = torch.where(live, weight + ww, weight)
+    q = torch.where(live, pw, q)
+  labels = torch.where(sampled[:, None, None], labels, torch.zeros_like(labels))
+  weight = torch.where(sampled[:, None], weight, neg)
+  return labels, weight, log_z

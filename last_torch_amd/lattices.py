@@ -18,6 +18,8 @@ weights once through the ``WeightFn`` plugin as a contiguous
   shortest_path   -> lt_viterbi
   align           -> lt_table_align (forced alignment; not in the reference);
                      past its range lt_table_num_backward (Max) compacted
+  sample          -> lt_den_forward / lt_table_forward (Log) + lt_table_sample
+                     (paths from the posterior; not in the reference)
 
 The device of the arc weights picks the implementation, as in the
 reference: ROCm tensors run the HIP kernels (FrameDependent and
@@ -515,6 +517,46 @@ class RecognitionLattice(nn.Module, Generic[T]):
     return (self._home(alignment_labels.reshape(*batch_dims, -1), frames),
             self._home(label_frames.reshape(*batch_dims, -1), frames),
             self._home(weights.reshape(batch_dims), frames))
+
+  def sample(self, frames: torch.Tensor, num_frames: torch.Tensor, num_samples: int, seed: int,
+             cache: Optional[T] = None):
+    """Alignment paths drawn from the lattice posterior p(pi) = exp(w(pi)) / Z,
+    Z the normaliser of `forward` (not in the reference): Gumbel-max on
+    Philox4x32-10 keyed by `seed`, walked backwards over the Log forward's
+    alpha -- the definition in include/lt_sample.h, so the same seed gives
+    the same paths on every device, and samples 0..S-1 do not depend on how
+    many more the call draws. FrameDependent with any context that has a
+    next-state table; FrameLabelDependent raises NotImplementedError.
+
+    Returns (alignment_labels [batch..., S, T] int64, path_weights
+    [batch..., S], log_z [batch...]): the true label y of the arc taken on
+    each frame (0 = blank, 0 on padding frames) and the sum of the path's arc
+    weights, so log p(pi) = path_weights - log_z. num_frames = 0 gives the
+    empty path (weight 0); an utterance whose log_z is not finite is
+    unsampled: labels all 0, weight -inf. No gradient flows through samples.
+    """
+    if not isinstance(self.alignment, alignments.FrameDependent):
+      raise NotImplementedError('sample implements FrameDependent alignments, got '
+                                f'{type(self.alignment).__name__}')
+    S = int(num_samples)
+    if S < 1:
+      raise ValueError(f'num_samples should be >= 1, but got {num_samples}')
+    W, nf, batch_dims, B, V, n, _ = self._prepare(cache, frames, num_frames)
+    with torch.no_grad():
+      W = W.detach()
+      if W.device.type == 'cpu':
+        labels, weights, log_z = cpu.sample(W, nf, self.context, S, seed)
+      else:
+        graph = self._graph(W.device)
+        if self._table_path():
+          log_z, alpha = _native.table_forward(graph, W, nf, _native.SEMIRING_LOG)
+        else:
+          log_z, alpha = _native.den_forward(W, nf, V, n, _native.SEMIRING_LOG)
+        labels, weights = _native.table_sample(graph, W, nf, log_z, alpha, S, seed)
+    T = W.shape[1]
+    return (self._home(labels.reshape(*batch_dims, S, T), frames),
+            self._home(weights.reshape(*batch_dims, S), frames),
+            self._home(log_z.reshape(batch_dims), frames))
 
   @staticmethod
   def _align_dense(graph, W, nf, lab, nl):
