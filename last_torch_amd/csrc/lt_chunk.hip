@@ -118,6 +118,29 @@ constexpr bool kBandMix = LT_CK_BANDMIX != 0;  // phase A: band steps between th
 #define LT_CK_EPIPE 0
 #endif
 constexpr bool kEpipe = LT_CK_EPIPE != 0;  // phase C den chains: the next frame's E a step ahead
+// phase C's serial path per workgroup (each switch on its own, for A/B runs):
+// LT_CK_NTERM: the numerator's marginal terms by the numerator waves as soon
+// as their chains end, not inside the frame's marginal job: 2 for the last
+// two jobs' frames (the ones the den chains' waves take when they end), 1
+// for every frame (measured slower: waves off the den chains are issue-bound
+// beside the other workgroups' prioritised chains, and this piles the
+// numerator work of all frames on two of them);
+// LT_CK_DENCOL: the marginal job's den pass over columns 1..V (+ the blank
+// column by lane), 2: xa by 16-byte loads where V = 32, 1: by dwords;
+// LT_CK_GSHIFT: the numerator-arc gather maps threads to (frame, position)
+// by shifts, no division
+#ifndef LT_CK_NTERM
+#define LT_CK_NTERM 2
+#endif
+constexpr int kNTerm = LT_CK_NTERM;
+#ifndef LT_CK_DENCOL
+#define LT_CK_DENCOL 2
+#endif
+constexpr int kDenCol = LT_CK_DENCOL;
+#ifndef LT_CK_GSHIFT
+#define LT_CK_GSHIFT 1
+#endif
+constexpr bool kGShift = LT_CK_GSHIFT != 0;
 #ifndef LT_WALK_SLOTS
 #define LT_WALK_SLOTS 3
 #endif
@@ -1528,8 +1551,9 @@ LT_DEVINL void store_dw(void* dW, long long e, float v) {
 // state's alpha and beta, W[0][0]
 constexpr int kFs = 8, kFsMa = 0, kFsA0 = 1, kFsMb = 2, kFsB0 = 3, kFsW00 = 4;
 // phase C's per-frame progress bits: den alpha / beta have passed the frame
-// (rows written, E_f read), numerator alpha / beta rows written
-constexpr int kFlA = 1, kFlB = 2, kFlNA = 4, kFlNB = 8, kFlAll = 15;
+// (rows written, E_f read), numerator alpha / beta rows written; kFlNT
+// (LT_CK_NTERM): the frame's numerator terms stand in place of those rows
+constexpr int kFlA = 1, kFlB = 2, kFlNA = 4, kFlNB = 8, kFlAll = 15, kFlNT = 16;
 
 template <bool BF16, int PPL, bool FULL>
 __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kernel(const CkArgs a) {
@@ -1705,7 +1729,36 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
   };
   // the numerator's arc weights leave W first (exact, log2); every read of
   // this pass issues before the barrier, every E store after it
-  if (!split) {
+  if (!split && kGShift) {
+    // LT_CK_GSHIFT: thread = (frame of the pass, position), PW positions x
+    // FPP frames a pass (128 x 2 for PPL 2, 64 x 4 for PPL 1): the position's
+    // offsets and masks once per thread, the frame by a shift; NU passes
+    // held in registers (a chunk of up to NU * FPP frames: no dead pass at
+    // the lengths the LDS budget gives long strings), the rest one by one
+    constexpr int PW = 64 * PPL, FPP = 64 * kMargWaves / PW, NU = PPL == 1 ? 2 : 3;
+    const int u = tid & (PW - 1), f0 = tid / PW;
+    const int uc = min(u, NPG - 1);
+    const int ob = boff[uc], ol = max(loff[uc], 0);
+    const bool inb = u < NP, inl = u >= 1 && u < NP;
+    const int FBi = (int)a.FB;
+    float2 g2[NU];
+#pragma unroll
+    for (int i = 0; i < NU; ++i) {
+      const unsigned char* fr = wch + min(FPP * i + f0, nt - 1) * FBi;
+      const float wb = ldsw<BF16>(fr, ob), wl = ldsw<BF16>(fr, ol);
+      g2[i] = make_float2(inb ? wb * kLog2e : -kInf, inl ? wl * kLog2e : -kInf);
+    }
+    for (int f = FPP * NU + f0; f < nt; f += FPP) {  // long chunks
+      const unsigned char* fr = wch + f * FBi;
+      const float wb = ldsw<BF16>(fr, ob), wl = ldsw<BF16>(fr, ol);
+      if (u < NPG) nw[f * NPG + u] = make_float2(inb ? wb * kLog2e : -kInf, inl ? wl * kLog2e : -kInf);
+    }
+#pragma unroll
+    for (int i = 0; i < NU; ++i) {
+      const int f = FPP * i + f0;
+      if (f < nt && u < NPG) nw[f * NPG + u] = g2[i];
+    }
+  } else if (!split) {
     float2 g2[4];
     const int nnw = nt * NPG;
 #pragma unroll
@@ -2054,43 +2107,9 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
   if (LT_CK_PRIO && role < 2) __builtin_amdgcn_s_setprio(0);
   CK_STAMP(2);
 
-  // ---- marginals, one wave per frame: den - num, each normalised by its
-  // frame total (alignments.py:311-317; numerator: reverse of :320-329).
-  // Den in rows: lane (y, h) = column y = lane & 31 of rows p = 2 m + h,
-  // then column 32 (lane p); arc (p, y) goes into q = y ? y : p. Den (p, y)
-  // = E[p][y] xa[p] xb[q] 2^(Ma + Mb + c - Z) except (0, 0), the only arc
-  // into the start state, taken in log2 (its beta may sit far above the
-  // core's; xb[0] = 0 keeps it out of the sum). Every other den term is
-  // <= 1 and the largest >= e^-61.
-  constexpr int NROW = 17;  // row pairs: p = 2 m + h <= 33
-  const int y = lane & 31, h = lane >> 5;
-  const bool ycol = y < R;  // FULL: every lane
-  int bo[PPL], lo[PPL];
-#pragma unroll
-  for (int r = 0; r < PPL; ++r) {
-    const int uc = min(lane + 64 * r, NP - 1);
-    bo[r] = boff[uc];
-    lo[r] = max(loff[uc], 0);
-  }
-  // frames as jobs in the order their inputs complete (middle first): a
-  // wave done with its recursion takes the next job and waits for that
-  // frame's four bits, so the marginals overlap the longer recursions
-  for (;;) {
-    int jb = 0;
-    if (lane == 0) jb = __hip_atomic_fetch_add(njob, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    jb = __builtin_amdgcn_readfirstlane(jb);
-    if (jb >= nt || LT_ABL(a, 16)) break;
-    const int f = ford[jb];
-    for (;;) {
-      const int bits = __builtin_amdgcn_readfirstlane(
-          __hip_atomic_load(fl + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-      if ((bits & kFlAll) == kFlAll) break;
-      __builtin_amdgcn_s_sleep(1);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    float* fb = eptr(f);  // E_f, then the frame's dW in place
-    // numerator terms (log2)
-    float sb[PPL], sl[PPL];
+  // ---- the numerator's marginal terms of frame f (log2 -> linear over the
+  // frame's total): they need the numerator rows only
+  auto num_terms = [&](int f, float* sb, float* sl) -> float {
     float mxn = -kInf;
 #pragma unroll
     for (int r = 0; r < PPL; ++r) {
@@ -2112,32 +2131,158 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
       zn += sb[r] + sl[r];
     }
     zn = wsum_u(zn);
-    const float gn = zn > 0.f ? g / zn : 0.f;
+    return zn > 0.f ? g / zn : 0.f;
+  };
+  // LT_CK_NTERM: the numerator chains end long before the den chains, so
+  // their waves form the terms of the last jobs' frames now (from job jpre
+  // on, even / odd rank in the marginals' order), behind the two numerator
+  // bits alone, and leave what the marginal job adds to dW, -sb gn and
+  // -sl gn, in the frame's an / bn rows (dead otherwise: the wave holds its
+  // whole row, the u - 1 neighbour included, before it overwrites)
+  const int jpre = kNTerm == 1 ? 0 : max(nt - 2, 0);  // the first job with its terms ready
+  if (kNTerm && role >= 2) {
+    for (int jb = jpre + role - 2; jb < nt; jb += 2) {
+      const int f = ford[jb];
+      wait_bits(f, kFlNA | kFlNB);
+      float sb[PPL], sl[PPL];
+      const float gn = num_terms(f, sb, sl);
+      __builtin_amdgcn_s_waitcnt(0xc07f);
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int r = 0; r < PPL; ++r) {
+        const int u = lane + 64 * r;
+        if (u < NP) {
+          an[f * NPG + u] = -sb[r] * gn;
+          bn[f * NPG + u] = -sl[r] * gn;
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+      mark(f, kFlNT);
+    }
+  }
+
+  // ---- marginals, one wave per frame: den - num, each normalised by its
+  // frame total (alignments.py:311-317; numerator: reverse of :320-329).
+  // Den in rows: lane (y, h) = column y = lane & 31 of rows p = 2 m + h,
+  // then column 32 (lane p); arc (p, y) goes into q = y ? y : p. Den (p, y)
+  // = E[p][y] xa[p] xb[q] 2^(Ma + Mb + c - Z) except (0, 0), the only arc
+  // into the start state, taken in log2 (its beta may sit far above the
+  // core's; xb[0] = 0 keeps it out of the sum). Every other den term is
+  // <= 1 and the largest >= e^-61.
+  // That row-pair layout is LT_CK_DENCOL = 0. The default,
+  // LT_CK_DENCOL: lane (y', h) = column y = y' + 1 of rows p = 16 h + m (+
+  // row 32 in h = 1), so the column's beta is one value per lane, and the
+  // blank column's arc (p, 0) by lane p < C; xa[16 h ..] by 16-byte loads
+  // where the row is 36 floats (V = 32). The product order per element is
+  // the same, (E xa) xb; only the order of the frame total's sum differs.
+  constexpr int NROW = 17;  // row pairs: p = 2 m + h <= 33
+  const int y = lane & 31, h = lane >> 5;
+  const bool ycol = y < R;  // FULL: every lane
+  int bo[PPL], lo[PPL];
+#pragma unroll
+  for (int r = 0; r < PPL; ++r) {
+    const int uc = min(lane + 64 * r, NP - 1);
+    bo[r] = boff[uc];
+    lo[r] = max(loff[uc], 0);
+  }
+  // frames as jobs in the order their inputs complete (middle first): a
+  // wave done with its recursion takes the next job and waits for that
+  // frame's four bits, so the marginals overlap the longer recursions
+  for (;;) {
+    int jb = 0;
+    if (lane == 0) jb = __hip_atomic_fetch_add(njob, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    jb = __builtin_amdgcn_readfirstlane(jb);
+    if (jb >= nt || LT_ABL(a, 16)) break;
+    const int f = ford[jb];
+    const bool pre = kNTerm && jb >= jpre;
+    const int want = pre ? (kFlA | kFlB | kFlNT) : kFlAll;
+    for (;;) {
+      const int bits = __builtin_amdgcn_readfirstlane(
+          __hip_atomic_load(fl + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+      if ((bits & want) == want) break;
+      __builtin_amdgcn_s_sleep(1);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    float* fb = eptr(f);  // E_f, then the frame's dW in place
+    // the numerator's additions to dW: ready in the frame's an / bn rows
+    // (LT_CK_NTERM), or formed here
+    float sb[PPL], sl[PPL];
+    if (pre) {
+#pragma unroll
+      for (int r = 0; r < PPL; ++r) {
+        const int uc = min(lane + 64 * r, NP - 1);
+        sb[r] = an[f * NPG + uc];
+        sl[r] = bn[f * NPG + uc];
+      }
+    } else {
+      const float gn = num_terms(f, sb, sl);
+#pragma unroll
+      for (int r = 0; r < PPL; ++r) {
+        sb[r] = -sb[r] * gn;
+        sl[r] = -sl[r] * gn;
+      }
+    }
     if (!a.local) {
       const float* xaf = xa + f * CP;
       const float* xbf = xb + f * CP;
-      const int yc = min(y, R - 1);
-      const float xby = xbf[yc];  // column y's beta (y >= 1)
-      // rows: E, xa[p] and xb[p] (the blank column's beta) for p = 2 m + h
-      float t[NROW], ra[NROW], rb[NROW];
-#pragma unroll
-      for (int m = 0; m < NROW; ++m) t[m] = fb[min(2 * m + h, C - 1) * R + yc];
-#pragma unroll
-      for (int m = 0; m < NROW; ++m) ra[m] = xaf[min(2 * m + h, C - 1)];
-#pragma unroll
-      for (int m = 0; m < NROW; ++m) rb[m] = xbf[min(2 * m + h, C - 1)];
-      // column 32 (C = 33 only): lane p < 33
+      float t[NROW], ra[NROW], tc, sum;
+      bool colc;
       const int pc = min(lane, C - 1);
-      float tc = fb[pc * R + (R - 1)] * xaf[pc] * xbf[R - 1];
-      const bool colc = R == 33 && lane < 33;
-      tc = colc ? tc : 0.f;
-      float sum = tc;
+      if constexpr (kDenCol != 0) {
+        const int yq = min(y + 1, R - 1);
+        const bool yl = y + 1 < R;
+        const float xby = xbf[yq];  // column y' + 1's beta
+        const float eb = fb[pc * R], xap = xaf[pc], xbp = xbf[pc];  // blank column: arc (p, 0) into p
 #pragma unroll
-      for (int m = 0; m < NROW; ++m) {
-        const bool live = ycol && 2 * m + h < C && (R < 33 || y < 32);
-        const float v = t[m] * ra[m] * (y ? xby : rb[m]);
-        t[m] = live ? v : 0.f;
-        sum += t[m];
+        for (int m = 0; m < 16; ++m) t[m] = fb[min(16 * h + m, C - 1) * R + yq];
+        t[16] = fb[min(32, C - 1) * R + yq];
+        if constexpr (FULL && kDenCol == 2) {
+#pragma unroll
+          for (int g4 = 0; g4 < 4; ++g4) {
+            const float4 x4 = *(const float4*)(xaf + 16 * h + 4 * g4);
+            ra[4 * g4 + 0] = x4.x;
+            ra[4 * g4 + 1] = x4.y;
+            ra[4 * g4 + 2] = x4.z;
+            ra[4 * g4 + 3] = x4.w;
+          }
+        } else {
+#pragma unroll
+          for (int m = 0; m < 16; ++m) ra[m] = xaf[min(16 * h + m, C - 1)];
+        }
+        ra[16] = xaf[min(32, C - 1)];
+        colc = lane < C;
+        tc = colc ? eb * xap * xbp : 0.f;
+        sum = tc;
+#pragma unroll
+        for (int m = 0; m < NROW; ++m) {
+          const bool live = yl && (m < 16 ? 16 * h + m < C : (h == 1 && C > 32));
+          const float v = t[m] * ra[m] * xby;
+          t[m] = live ? v : 0.f;
+          sum += t[m];
+        }
+      } else {
+        const int yc = min(y, R - 1);
+        const float xby = xbf[yc];  // column y's beta (y >= 1)
+        // rows: E, xa[p] and xb[p] (the blank column's beta) for p = 2 m + h
+        float rb[NROW];
+#pragma unroll
+        for (int m = 0; m < NROW; ++m) t[m] = fb[min(2 * m + h, C - 1) * R + yc];
+#pragma unroll
+        for (int m = 0; m < NROW; ++m) ra[m] = xaf[min(2 * m + h, C - 1)];
+#pragma unroll
+        for (int m = 0; m < NROW; ++m) rb[m] = xbf[min(2 * m + h, C - 1)];
+        // column 32 (C = 33 only): lane p < 33
+        tc = fb[pc * R + (R - 1)] * xaf[pc] * xbf[R - 1];
+        colc = R == 33 && lane < 33;
+        tc = colc ? tc : 0.f;
+        sum = tc;
+#pragma unroll
+        for (int m = 0; m < NROW; ++m) {
+          const bool live = ycol && 2 * m + h < C && (R < 33 || y < 32);
+          const float v = t[m] * ra[m] * (y ? xby : rb[m]);
+          t[m] = live ? v : 0.f;
+          sum += t[m];
+        }
       }
       sum = wsum_u(sum);
       const float* fsf = fs + f * kFs;
@@ -2157,13 +2302,22 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
       const float m00 = g * __builtin_amdgcn_exp2f(v00 - zl);
       __builtin_amdgcn_s_waitcnt(0xc07f);
       __builtin_amdgcn_wave_barrier();
+      if constexpr (kDenCol != 0) {
 #pragma unroll
-      for (int m = 0; m < NROW; ++m) {
-        const int p = 2 * m + h;
-        if (ycol && p < C && (R < 33 || y < 32))
-          fb[p * R + y] = (m == 0 && lane == 0) ? m00 : t[m] * mult;
+        for (int m = 0; m < NROW; ++m) {
+          const int p = m < 16 ? 16 * h + m : 32;
+          if (y + 1 < R && (m < 16 ? p < C : (h == 1 && C > 32))) fb[p * R + y + 1] = t[m] * mult;
+        }
+        if (colc) fb[pc * R] = lane == 0 ? m00 : tc * mult;
+      } else {
+#pragma unroll
+        for (int m = 0; m < NROW; ++m) {
+          const int p = 2 * m + h;
+          if (ycol && p < C && (R < 33 || y < 32))
+            fb[p * R + y] = (m == 0 && lane == 0) ? m00 : t[m] * mult;
+        }
+        if (colc) fb[pc * R + (R - 1)] = tc * mult;
       }
-      if (colc) fb[pc * R + (R - 1)] = tc * mult;
     } else {
       __builtin_amdgcn_s_waitcnt(0xc07f);
       __builtin_amdgcn_wave_barrier();
@@ -2174,8 +2328,8 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
     for (int r = 0; r < PPL; ++r) {
       const int u = lane + 64 * r;
       if (u < NP) {
-        atomicAdd(fb + bo[r], -sb[r] * gn);
-        if (u >= 1) atomicAdd(fb + lo[r], -sl[r] * gn);
+        atomicAdd(fb + bo[r], sb[r]);
+        if (u >= 1) atomicAdd(fb + lo[r], sl[r]);
       }
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);

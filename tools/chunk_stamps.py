@@ -36,15 +36,32 @@ if os.environ.get('LT_CK_LDS_PAD'):
   e1.record()
   torch.cuda.synchronize()
   print(f'LDS pad {os.environ["LT_CK_LDS_PAD"]}: {e0.elapsed_time(e1) / 10:.3f} ms per call')
-s = st.cpu().numpy().reshape(-1, 8)[:B * (-(-T // 6))]
-s = s[s[:, 0] > 0]
+s = st.cpu().numpy().reshape(-1, 8)
+# the chunk workgroups: a row per block of the launch, the walking workgroups
+# in front of them (when the launch finishes the walks) leave mark 1 empty
+blk = np.nonzero((s[:, 0] > 0) & (s[:, 1] > 0))[0]
+s = s[blk]
 segs = [('DMA+tables', 0, 1), ('nw + E', 1, 5), ('recursions', 5, 2), ('marginals', 2, 3),
         ('dW stream', 3, 4)]
-for nm, i, j in segs:
-  if not s[:, j].any():
-    continue
-  d = s[:, j] - s[:, i]
-  print(f'{nm:12s} median {np.median(d):8.0f}  p90 {np.percentile(d, 90):8.0f} cycles')
-tot = s[:, 4] - s[:, 0]
-print(f'{"total":12s} median {np.median(tot):8.0f}  p90 {np.percentile(tot, 90):8.0f}; '
-      f'workgroups {len(s)}, span {s[:, 4].max() - s[:, 0].min()} cycles')
+
+
+def report(s, head):
+  for nm, i, j in segs:
+    if not s[:, j].any():
+      continue
+    d = s[:, j] - s[:, i]
+    print(f'{head}{nm:12s} median {np.median(d):8.0f}  p90 {np.percentile(d, 90):8.0f} cycles')
+  tot = s[:, 4] - s[:, 0]
+  print(f'{head}{"total":12s} median {np.median(tot):8.0f}  p90 {np.percentile(tot, 90):8.0f}; '
+        f'workgroups {len(s)}')
+
+
+report(s, '')
+print(f'span {s[:, 4].max() - s[:, 0].min()} cycles')
+# the marks are wave 0's, whose recursion rotates with the block (LT_CK_ROT
+# = 1: role (block >> 3) & 3): per role, `recursions` is that chain's own
+# length and `marginals` what follows it up to the workgroup's last barrier
+for role, nm in enumerate(('den alpha', 'den beta', 'num alpha', 'num beta')):
+  sel = ((blk >> 3) & 3) == role
+  if sel.any():
+    report(s[sel], f'[{nm:9s}] ')
