@@ -485,5 +485,7 @@ const char* lt_version(void);
 #include "lt_align.h"
 /* Sampling alignment paths from the lattice posterior, likewise. */
 #include "lt_sample.h"
+/* Posterior means of arc values and their gradients, likewise. */
+#include "lt_expect.h"
 
 #endif /* LT_LATTICE_H_ */

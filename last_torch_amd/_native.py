@@ -96,6 +96,8 @@ _SIG = {
     'lt_table_sample_workspace_bytes': [_G, _TP, _I32, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_sample': [_G, _TP, _P, _P, _P, _P, _I32, ctypes.c_uint64, _P, _P, _P,
                         ctypes.c_size_t, _P],
+    'lt_table_expectation_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
+    'lt_table_expectation': [_G, _TP] + [_P] * 8 + [ctypes.c_size_t, _P],
     'lt_joint_weights_workspace_bytes': [ctypes.c_int64, _I32, _I32,
                                          ctypes.POINTER(ctypes.c_size_t)],
     'lt_joint_weights': [ctypes.c_int64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P,
@@ -120,11 +122,13 @@ _SIG = {
                    _P],
 }
 # the functions each header of the C ABI declares: include/lt_align.h (forced
-# alignment), include/lt_sample.h (path sampling) and include/lt_lattice.h
-# (everything else)
+# alignment), include/lt_sample.h (path sampling), include/lt_expect.h
+# (posterior means of arc values) and include/lt_lattice.h (everything else)
 EXPORTED_ALIGN = ('lt_table_align_workspace_bytes', 'lt_table_align')
 EXPORTED_SAMPLE = ('lt_table_sample_workspace_bytes', 'lt_table_sample')
-EXPORTED = (tuple(n for n in _SIG if n not in EXPORTED_ALIGN + EXPORTED_SAMPLE) +
+EXPORTED_EXPECT = ('lt_table_expectation_workspace_bytes', 'lt_table_expectation')
+EXPORTED = (tuple(n for n in _SIG
+                  if n not in EXPORTED_ALIGN + EXPORTED_SAMPLE + EXPORTED_EXPECT) +
             ('lt_last_error', 'lt_version'))
 
 
@@ -690,6 +694,32 @@ def table_sample(graph, W, num_frames, log_z, alpha, num_samples, seed):
                                _ptr(labels), _ptr(weight), _ptr(ws), nbytes.value, _stream()),
          'lt_table_sample')
   return labels, weight
+
+
+def table_expectation(graph, W, values, num_frames, want_marg=True, want_cov=True):
+  """lt_table_expectation: (expected [B], log_z [B], marg or None, cov or
+  None) for arc values [B,T,C,V+1]; marg = dE/dvalues = d log_z/dW (the arc
+  marginals) and cov = dE/dW, both fp32 [B,T,C,V+1] without an incoming
+  gradient. Neither wanted: the forward kernel only."""
+  pb = _tproblem(graph, W)
+  B = W.shape[0]
+  if tuple(values.shape) != tuple(W.shape):
+    raise ValueError(f'values {tuple(values.shape)} do not match the arc weights '
+                     f'{tuple(W.shape)}')
+  values = values.to(device=W.device, dtype=torch.float32).contiguous()
+  nbytes = ctypes.c_size_t(0)
+  _check(lib().lt_table_expectation_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
+                                                    ctypes.byref(nbytes)),
+         'lt_table_expectation_workspace_bytes')
+  ws = torch.empty([max(nbytes.value, 1)], dtype=torch.uint8, device=W.device)
+  expected, log_z = _f32([B], W), _f32([B], W)
+  marg = _f32(tuple(W.shape), W) if want_marg else None
+  cov = _f32(tuple(W.shape), W) if want_cov else None
+  _check(lib().lt_table_expectation(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W),
+                                    _ptr(values), _ptr(num_frames), _ptr(expected), _ptr(log_z),
+                                    _ptr(marg), _ptr(cov), _ptr(ws), nbytes.value, _stream()),
+         'lt_table_expectation')
+  return expected, log_z, marg, cov
 
 
 JOINT_BF16, JOINT_SPLIT = 0, 1  # lt_joint_weights_ex precisions (include/lt_lattice.h)

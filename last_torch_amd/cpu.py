@@ -33,6 +33,10 @@ MaxTropical's first-argmax rule prefers the blank, then fewer expansions.
   sample        (not in the reference) paths from the posterior exp(w) / Z:
                                       Gumbel-max on Philox4x32-10, walked
                                       backwards over alpha (lt_sample.h)
+  expectation   (not in the reference) posterior mean of an arc-additive path
+                                      value (lt_expect.h): the arc marginals
+                                      by autograd with a graph, so the result
+                                      is differentiable by ordinary autograd
 """
 import torch
 
@@ -223,6 +227,36 @@ def align(W: torch.Tensor, nf: torch.Tensor, labels: torch.Tensor, nl: torch.Ten
   b, t, u = torch.nonzero(taken, as_tuple=True)
   out[b, t, slot[b, t, u]] = true[b, u]
   return out.reshape(B, T * A), label_frames, dist
+
+
+def expectation(W: torch.Tensor, values: torch.Tensor, nf: torch.Tensor,
+                context: contexts.ContextDependency) -> tuple[torch.Tensor, torch.Tensor]:
+  """(E [B], log_z [B]) of include/lt_expect.h on the FrameDependent
+  denominator lattice: E = sum_a m_a v_a with m = d log_z / dW taken with a
+  graph, so E and log_z are differentiable w.r.t. W, and E w.r.t. values, by
+  ordinary autograd (d E / dW is the second derivative of log_z). Runs in W's
+  dtype. Edge rules: an arc with m = 0 (w = -inf, padding) contributes nothing
+  and its value is not read into the arithmetic; an utterance whose log_z is
+  not finite gives E = 0 and zero gradients, log_z as computed."""
+  alignment = alignments.FrameDependent()
+  wants_graph = torch.is_grad_enabled() and (W.requires_grad or values.requires_grad)
+  with torch.no_grad():
+    lz0, _ = den_forward(W, nf, context, alignment, semirings.Log)
+  fin = torch.isfinite(lz0)
+  with torch.enable_grad():
+    # utterances without a finite log_z run on zero weights, detached from W
+    Ws = torch.where(fin[:, None, None, None], W, torch.zeros_like(W))
+    if not Ws.requires_grad:
+      Ws = Ws.requires_grad_()
+    log_z, _ = den_forward(Ws, nf, context, alignment, semirings.Log)
+    (m,) = torch.autograd.grad(log_z.sum(), Ws, create_graph=True)
+    v = torch.where(m > 0, values.to(W.dtype), torch.zeros_like(m))
+    expected = (m * v).sum(dim=(1, 2, 3))
+    expected = torch.where(fin, expected, torch.zeros_like(expected))
+    log_z = torch.where(fin, log_z, lz0)
+  if not wants_graph:
+    expected, log_z = expected.detach(), log_z.detach()
+  return expected, log_z
 
 
 # ---------------------------------------------------------------------------

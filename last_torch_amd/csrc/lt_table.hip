@@ -22,7 +22,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "lt_kernels.h"
+#include "lt_table_common.h"
 
 namespace {
 
@@ -59,53 +59,6 @@ struct TArgs {
   float* lx;
 };
 
-// Copies the graph arrays to LDS at g (ints: in_off [C+1], in_arc [C*V],
-// table [C*V]) when GST, and returns the arrays to use (compile-time choice,
-// so the compiler knows which memory every access goes to).
-template <bool GST>
-LT_DEVINL void t_graph(const TArgs& a, int* g, const int** in_off, const int** in_arc,
-                       const int** table) {
-  if constexpr (!GST) {
-    *in_off = a.in_off;
-    *in_arc = a.in_arc;
-    *table = a.table;
-    return;
-  }
-  const int C = a.C, CV = a.C * a.V;
-  for (int i = threadIdx.x; i <= C; i += blockDim.x) g[i] = a.in_off[i];
-  for (int i = threadIdx.x; i < CV; i += blockDim.x) {
-    const int id = a.in_arc[i];
-    const int p = id / a.V;
-    g[C + 1 + i] = p | ((id - p * a.V) << 16);  // DenGraphP packing
-    g[C + 1 + CV + i] = a.table[i];
-  }
-  *in_off = g;
-  *in_arc = g + C + 1;
-  *table = g + C + 1 + CV;
-}
-
-LT_DEVINL float t_safe(float x) { return __builtin_isfinite(x) ? x : 0.f; }
-// _LogAddExp (semirings.py:248-255)
-LT_DEVINL float t_lae(float a, float b) {
-  const float m = fmaxf(a, b);
-  const float c = t_safe(m);
-  return c + lt_log_acc(lt_exp(a - c) + lt_exp(b - c));
-}
-// running logsumexp (m, s): the result is m + log(s) with the safe max
-struct Lse {
-  float m = -kInf, s = 0.f;
-  LT_DEVINL void add(float x) {
-    if (x == -kInf) return;
-    if (x > m) {
-      s = s * lt_exp(m - x) + 1.f;
-      m = x;
-    } else {
-      s += lt_exp(x - m);
-    }
-  }
-  LT_DEVINL float get() const { return s > 0.f ? m + lt_log_acc(s) : -kInf; }
-};
-
 template <int SR>
 LT_DEVINL float t_zero() { return SR == M_REAL ? 0.f : -kInf; }
 template <int SR>
@@ -121,70 +74,9 @@ constexpr int kTabMaxThreads = 512;
 #define LT_TAB_DENSE 1  // the dense-bigram FrameLabelDependent kernels (diagnostic builds: 0 = generic)
 #endif
 
-// Log vectors are kept relative to an integer offset near their maximum
-// (exact in fp32), so a recursion over T frames rounds small numbers, not
-// values of magnitude |log_z| (the tuned kernels' scheme): the
-// offset after a frame is floor(max) of its new vector.
-// That offset without a pass of its own: the threads that write the new
-// vector's values fold them into an LDS slot (ds_max on an order-preserving
-// int image) and, after the barrier that publishes the vector, every thread
-// reads the slot. Three slots rotate: frame t writes slot t % 3, reads it
-// after its barrier, and resets slot (t + 1) % 3 for the next frame (the
-// last frame that read it was t - 2).
-LT_DEVINL int t_ord(float f) {
-  const int i = __float_as_int(f);
-  return i >= 0 ? i : i ^ 0x7fffffff;
-}
-LT_DEVINL float t_unord(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
-struct MaxSlots {
-  int* s;  // [3] in LDS
-  LT_DEVINL void init() const {
-    if (threadIdx.x < 3) s[threadIdx.x] = t_ord(-kInf);
-  }
-  LT_DEVINL void put(int t, float v) const { atomicMax(s + t % 3, t_ord(v)); }
-  LT_DEVINL void reset_next(int t) const {
-    if (threadIdx.x == 0) s[(t + 1) % 3] = t_ord(-kInf);
-  }
-  // after the barrier: the integer offset floor(max) (0 when not finite)
-  LT_DEVINL float shift(int t) const {
-    const float m = t_unord(s[t % 3]);
-    return __builtin_isfinite(m) ? floorf(m) : 0.f;
-  }
-};
-
-// Graph accessors: the context lattice (states p, in-arcs from the CSR) and
-// the string acceptor (positions u, one in-arc from u-1; lattices.py:314-338).
-struct DenGraph {
-  const int* in_off;
-  const int* in_arc;
-  int V, R;
-  LT_DEVINL int blank(int q) const { return q * R; }
-  LT_DEVINL int nin(int q) const { return in_off[q + 1] - in_off[q]; }
-  LT_DEVINL int pos0(int q) const { return in_off[q]; }
-  LT_DEVINL void arc(int pos, int q, int* src, int* widx) const {
-    (void)q;
-    const int id = in_arc[pos];
-    const int p = id / V;
-    *src = p;
-    *widx = p * R + (id - p * V) + 1;
-  }
-};
-// The LDS copy of the CSR holds src | (label - 1) << 16 (no division).
-struct DenGraphP {
-  const int* in_off;
-  const int* in_arc;
-  int V, R;
-  LT_DEVINL int blank(int q) const { return q * R; }
-  LT_DEVINL int nin(int q) const { return in_off[q + 1] - in_off[q]; }
-  LT_DEVINL int pos0(int q) const { return in_off[q]; }
-  LT_DEVINL void arc(int pos, int q, int* src, int* widx) const {
-    (void)q;
-    const int v = in_arc[pos];
-    const int p = v & 0xffff;
-    *src = p;
-    *widx = p * R + (v >> 16) + 1;
-  }
-};
+// Graph accessors: the context lattice's DenGraph / DenGraphP
+// (lt_table_common.h, with the other helpers lt_expect.hip shares) and the
+// string acceptor (positions u, one in-arc from u-1; lattices.py:314-338).
 struct NumGraph {
   const int* ctx;  // [S] ctx state * R
   const int* yn;   // [S] label class of the arc leaving u
@@ -208,32 +100,6 @@ struct NumGraphC {
     (void)pos;
     *src = u - 1;
     *widx = 2 * u - 1;
-  }
-};
-
-// Register staging of a strided per-frame gather (element e -> ld(e)): the
-// next frame's values are loaded while this frame computes, so a frame costs
-// no memory round trip of its own (N rounds per thread; the rest is loaded
-// directly when stored)
-template <int N>
-struct RegStage {
-  float r[N];
-  template <typename F>
-  LT_DEVINL void fetch(int n, const F& ld) {
-#pragma unroll
-    for (int u = 0; u < N; ++u) {
-      const int e = u * blockDim.x + threadIdx.x;
-      r[u] = e < n ? ld(e) : 0.f;
-    }
-  }
-  template <typename F>
-  LT_DEVINL void store(float* dst, int n, const F& ld) const {
-#pragma unroll
-    for (int u = 0; u < N; ++u) {
-      const int e = u * blockDim.x + threadIdx.x;
-      if (e < n) dst[e] = r[u];
-    }
-    for (int e = N * blockDim.x + threadIdx.x; e < n; e += blockDim.x) dst[e] = ld(e);
   }
 };
 
@@ -274,22 +140,6 @@ LT_DEVINL float t_reduce(const G& g, int q, const float* x, const WR& wr, int* a
       r += x[src] * wr(wi);
     }
     return r;
-  }
-}
-
-// Merge a running logsumexp over G aligned lanes (xor shuffles; every lane of
-// the wave takes part) -- the lanes then hold the group's total.
-template <int G>
-LT_DEVINL void lse_merge(Lse& l) {
-  for (int o = 1; o < G; o <<= 1) {
-    const float m2 = __shfl_xor(l.m, o, 64), s2 = __shfl_xor(l.s, o, 64);
-    const float M = fmaxf(l.m, m2);
-    if (M == -kInf) {
-      l.s = 0.f;
-    } else {
-      l.s = l.s * lt_exp(l.m - M) + s2 * lt_exp(m2 - M);
-      l.m = M;
-    }
   }
 }
 
@@ -389,42 +239,6 @@ LT_DEVINL void t_walk(const TArgs& a, int b, int* ctx, int* yn) {
     if (u < a.U && y != 0) c = a.table[c * a.V + y - 1];
   }
 }
-
-// Frame staging: the first kPf*blockDim weights of frame t+1 are loaded into
-// registers while frame t is processed (one memory round trip per frame,
-// hidden), the rest of a large frame in batches of kPf loads per thread.
-constexpr int kPf = 8;
-template <bool BF16>
-struct FrameStage {
-  float r[kPf];
-  LT_DEVINL void fetch(const unsigned char* wf, long long FR) {
-#pragma unroll
-    for (int u = 0; u < kPf; ++u) {
-      const long long e = (long long)u * blockDim.x + threadIdx.x;
-      r[u] = (wf && e < FR) ? ldw<BF16>(wf, e) : 0.f;
-    }
-  }
-  LT_DEVINL void store(float* wl, const unsigned char* wf, long long FR) {
-#pragma unroll
-    for (int u = 0; u < kPf; ++u) {
-      const long long e = (long long)u * blockDim.x + threadIdx.x;
-      if (e < FR) wl[e] = r[u];
-    }
-    for (long long e0 = (long long)kPf * blockDim.x; e0 < FR; e0 += (long long)kPf * blockDim.x) {
-      float t[kPf];
-#pragma unroll
-      for (int u = 0; u < kPf; ++u) {
-        const long long e = e0 + (long long)u * blockDim.x + threadIdx.x;
-        t[u] = e < FR ? ldw<BF16>(wf, e) : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < kPf; ++u) {
-        const long long e = e0 + (long long)u * blockDim.x + threadIdx.x;
-        if (e < FR) wl[e] = t[u];
-      }
-    }
-  }
-};
 
 // ---- string forward in Log (lattices.py:250-377, alignments.py:320-329 and
 // :420-432 for FrameLabelDependent): every position as an exact integer part
@@ -2513,7 +2327,6 @@ int t_fail(int code, const char* msg) { return lt_impl::set_error(code, msg); }
 int t_hip(hipError_t e, const char* what) {
   return e == hipSuccess ? LT_OK : lt_impl::set_error(LT_EHIP, what);
 }
-constexpr int kTabLds = 160 * 1024;
 
 int t_check(const lt_graph* g, const lt_table_problem* pb) {
   if (!g || !pb) return t_fail(LT_EINVAL, "null graph / problem");
@@ -2578,8 +2391,6 @@ int t_launch2(KF k, int grid, int lds_bytes, hipStream_t st, const TArgs& a1, co
 }
 
 int fwd_lds(int S) { return 4 * (4 * S) + 8 * S; }
-// stage a frame in LDS when it fits beside the state vectors
-constexpr int kStageBudget = 144 * 1024;
 
 template <bool BF16, bool STG>
 int launch_t_fwd_s(int sr, bool num, bool vit, const TArgs& a, int lds, hipStream_t st) {

@@ -20,6 +20,9 @@ weights once through the ``WeightFn`` plugin as a contiguous
                      past its range lt_table_num_backward (Max) compacted
   sample          -> lt_den_forward / lt_table_forward (Log) + lt_table_sample
                      (paths from the posterior; not in the reference)
+  expectation     -> lt_table_expectation (posterior mean of arc values with
+                     its gradients; not in the reference), also behind
+                     entropy(differentiable=True)
 
 The device of the arc weights picks the implementation, as in the
 reference: ROCm tensors run the HIP kernels (FrameDependent and
@@ -228,6 +231,40 @@ class _TableDenFn(torch.autograd.Function):
     W, nf, dist, alpha = ctx.saved_tensors
     dW = _native.table_den_backward(ctx.graph, W, nf, ctx.sid, dist, alpha, g.float())
     return dW, None, None, None
+
+
+class _ExpectFn(torch.autograd.Function):
+  """(E, log_z) of include/lt_expect.h on the table kernels: the forward is
+  ONE lt_table_expectation call that also writes the gradient tensors the
+  inputs need (marg = dE/dvalues = d log_z/dW, cov = dE/dW); the backward
+  combines them with the incoming gradients. A second backward (retain_graph)
+  recomputes them. Not twice differentiable."""
+
+  @staticmethod
+  def forward(ctx, W, values, nf, graph):
+    need_w, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    expected, log_z, marg, cov = _native.table_expectation(
+        graph, W, values, nf, want_marg=need_w or need_v, want_cov=need_w)
+    ctx.graph, ctx.marg, ctx.cov = graph, marg, cov
+    ctx.save_for_backward(W, values, nf)
+    return expected, log_z
+
+  @staticmethod
+  def backward(ctx, g_e, g_z):
+    W, values, nf = ctx.saved_tensors
+    need_w, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    marg, cov = ctx.marg, ctx.cov
+    ctx.marg = ctx.cov = None
+    if marg is None and (need_w or need_v):  # a second backward through the same graph
+      _, _, marg, cov = _native.table_expectation(ctx.graph, W, values, nf,
+                                                  want_marg=True, want_cov=need_w)
+    g_e = g_e.float()[:, None, None, None]
+    dW = dv = None
+    if need_w:
+      dW = (g_e * cov + g_z.float()[:, None, None, None] * marg).to(W.dtype)
+    if need_v:
+      dv = (g_e * marg).to(values.dtype)
+    return dW, dv, None, None
 
 
 class _TableNumFn(torch.autograd.Function):
@@ -709,13 +746,62 @@ class RecognitionLattice(nn.Module, Generic[T]):
     return ((self._home(log_z.reshape(batch_dims), frames),
              self._home(log_sum.reshape(batch_dims), frames)), None)
 
+  def _expect(self, W, values, nf):
+    """(E [B], log_z [B]) for flattened arc weights and values on W's device:
+    cpu.expectation (plain autograd) or _ExpectFn (lt_table_expectation)."""
+    if W.device.type == 'cpu':
+      return cpu.expectation(W, values.to(W.device), nf, self.context)
+    return _ExpectFn.apply(W, values.to(W.device), nf, self._graph(W.device))
+
+  def expectation(self, frames: torch.Tensor, num_frames: torch.Tensor, values: torch.Tensor,
+                  cache: Optional[T] = None):
+    """Posterior mean of an arc-additive path value (not in the reference;
+    the definition is in include/lt_expect.h): with p(pi) = exp(w(pi)) / Z
+    over the alignment paths of `forward`'s denominator lattice,
+    expected = sum_pi p(pi) sum_{a in pi} values[a]. `values` has the layout
+    of the arc weights, [batch..., T, C, V+1] ([..., 0] the blank arc of a
+    state, [..., y] its label-y arc), and may have any sign.
+
+    Returns (expected [batch...], log_z [batch...]). Both are differentiable
+    w.r.t. the weight function through the arc weights, and `expected` also
+    w.r.t. `values`: d expected / d values is the arc marginal m_a and
+    d expected / d w_a = m_a (E[v | a] - expected). On ROCm tensors the
+    gradients come from one lt_table_expectation call with the forward and are
+    not twice differentiable; on CPU tensors they are plain autograd.
+    An arc of weight -inf contributes nothing and its value is ignored (NaN
+    or inf there is harmless); num_frames = 0 gives (0, 0); an utterance whose
+    log_z is not finite gives expected = 0 and zero gradients. FrameDependent
+    with any context that has a next-state table; FrameLabelDependent raises
+    NotImplementedError."""
+    if not isinstance(self.alignment, alignments.FrameDependent):
+      raise NotImplementedError('expectation implements FrameDependent alignments, got '
+                                f'{type(self.alignment).__name__}')
+    W, nf, batch_dims, B, _, _, _ = self._prepare(cache, frames, num_frames)
+    values = torch.as_tensor(values)
+    if tuple(values.shape) != (*batch_dims, *W.shape[1:]):
+      raise ValueError(f'values should have the shape of the arc weights '
+                       f'{(*batch_dims, *W.shape[1:])}, but got {tuple(values.shape)}')
+    expected, log_z = self._expect(W, values.reshape(W.shape), nf)
+    return (self._home(expected.reshape(batch_dims), frames),
+            self._home(log_z.reshape(batch_dims), frames))
+
   def entropy(self, frames: torch.Tensor, num_frames: torch.Tensor,
-              cache: Optional[T] = None) -> torch.Tensor:
+              cache: Optional[T] = None, differentiable: bool = False) -> torch.Tensor:
     """Entropy (nats) of the alignment-path distribution p(path) = exp(w_path)
     / Z of every utterance: H = log Z - E_p[w_path], the lattice entropy the
     LogLogExpectation semiring computes (tests/semirings_test.py:305-312:
     entropy = log_z + exp(log_sum - log_z)), here for weights of any sign.
-    Values only (no gradient)."""
+    Values only (no gradient) by default. differentiable=True returns H with
+    a graph w.r.t. the weight function (entropy regularisation): one
+    arc_weights call, then `expectation`'s function on (W, -W); FrameDependent
+    only, and on ROCm tensors not twice differentiable."""
+    if differentiable:
+      if not isinstance(self.alignment, alignments.FrameDependent):
+        raise NotImplementedError('entropy(differentiable=True) implements FrameDependent '
+                                  f'alignments, got {type(self.alignment).__name__}')
+      W, nf, batch_dims, _, _, _, _ = self._prepare(cache, frames, num_frames)
+      neg_w, log_z = self._expect(W, -W.float(), nf)  # E_p[-w_path]
+      return self._home((log_z + neg_w).reshape(batch_dims), frames)
     log_z, mw, batch_dims = self._expectation(cache, frames, num_frames)
     return self._home((log_z - mw).reshape(batch_dims), frames)
 
