@@ -141,6 +141,26 @@ constexpr int kDenCol = LT_CK_DENCOL;
 #define LT_CK_GSHIFT 1
 #endif
 constexpr bool kGShift = LT_CK_GSHIFT != 0;
+// LT_CK_DPPRED: the wave reductions (wmax_u / wsum_u) with one DPP-modified
+// v_max_f32 / v_add_f32 per stage (see wred)
+#ifndef LT_CK_DPPRED
+#define LT_CK_DPPRED 1
+#endif
+constexpr bool kDppRed = LT_CK_DPPRED != 0;
+// LT_CK_GEOM: ck_marg_kernel instantiated per chunk length for V = 32 (see
+// the kernel); LT_CHUNK_GENERIC=1 forces the run-time kernel per call
+#ifndef LT_CK_GEOM
+#define LT_CK_GEOM 1
+#endif
+constexpr bool kGeom = LT_CK_GEOM != 0;
+// LT_CK_PREDST: the den steps' single-lane and partial-wave LDS stores as
+// unconditional stores with the address (and value) selected per lane, the
+// idle lanes landing in unused slots of the wave's own buf row. Off: measured
+// no gain alone (-0.2 us of 310, profiles/chunk_issue_diet.txt), same bits
+#ifndef LT_CK_PREDST
+#define LT_CK_PREDST 0
+#endif
+constexpr bool kPredSt = LT_CK_PREDST != 0;
 #ifndef LT_WALK_SLOTS
 #define LT_WALK_SLOTS 3
 #endif
@@ -217,6 +237,15 @@ LT_DEVINL float half_sum(float v) {
 LT_DEVINL float half_other(float v) {
   auto p = __builtin_amdgcn_permlane32_swap(__float_as_int(v), __float_as_int(v), false, false);
   return (threadIdx.x & 32) ? __int_as_float(p[0]) : __int_as_float(p[1]);
+}
+// max of lanes l and l ^ 32 in both (LT_CK_DPPRED: one v_max_f32 on the
+// swap's two results, no select of the other half's and no canonicalising
+// of the operands; a quiet NaN operand is dropped as fmaxf drops it)
+LT_DEVINL float half_max(float v) {
+  auto p = __builtin_amdgcn_permlane32_swap(__float_as_int(v), __float_as_int(v), false, false);
+  float r;
+  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(__int_as_float(p[0])), "v"(__int_as_float(p[1])));
+  return r;
 }
 // lane l gets v of lane l-1 (lane 0: fill)
 LT_DEVINL float from_prev(float v, float fill) {
@@ -342,8 +371,22 @@ LT_DEVINL void dma_range(const unsigned char* base, long long off, long long byt
 // wave-uniform max / sum over all 64 lanes with DPP only (no LDS round trip):
 // butterflies inside each row of 16, then row_bcast:15 / row_bcast:31 fold
 // rows 0-1 into 2-3, and lane 63 holds the total
+// LT_CK_DPPRED: every stage as one v_max_f32 / v_add_f32 with a DPP source
+// operand (dpp_max / dpp_add, then rows_fold) in place of v_mov_dpp + two
+// canonicalising v_max + the op. Same stages in the same order, the total
+// in lane 63. Without the canonicalising pre-ops v_max_f32 drops a quiet NaN
+// operand as fmaxf does but returns a signalling NaN quieted: the callers'
+// values come out of arithmetic (or, in phase A's frame max, out of
+// max3_raw, which never quieted either), so no signalling NaN reaches it
+// unless W itself holds one, and that W fails phase A's e >= 0 test as any
+// NaN does.
 template <bool MAX>
 LT_DEVINL float wred(float v) {
+  if constexpr (kDppRed) {
+    if constexpr (MAX) v = dpp_max<3>(dpp_max<2>(dpp_max<1>(dpp_max<0>(v))));
+    else v = dpp_add<3>(dpp_add<2>(dpp_add<1>(dpp_add<0>(v))));
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rows_fold<MAX>(v)), 63));
+  }
   auto op = [](float x, float y) { return MAX ? fmaxf(x, y) : x + y; };
   v = op(v, xchg<0>(v));
   v = op(v, xchg<1>(v));
@@ -827,7 +870,7 @@ LT_DEVINL void transfer_role(const CkArgs& a, int b, int k, int wave) {
     float cm = fmaxf(max3_raw(D[0], D[1], D[2]), max3_raw(D[3], D[4], D[5]));
 #pragma unroll
     for (int r = 6; r < 16; r += 2) cm = max3_raw(cm, D[r], D[r + 1]);
-    cm = fmaxf(cm, half_other(cm));
+    cm = kDppRed ? half_max(cm) : fmaxf(cm, half_other(cm));
     int e;
     frexpf(cm, &e);
     e = cm > 0.f ? e : 0;
@@ -1555,11 +1598,25 @@ constexpr int kFs = 8, kFsMa = 0, kFsA0 = 1, kFsMb = 2, kFsB0 = 3, kFsW00 = 4;
 // (LT_CK_NTERM): the frame's numerator terms stand in place of those rows
 constexpr int kFlA = 1, kFlB = 2, kFlNA = 4, kFlNB = 8, kFlAll = 15, kFlNT = 16;
 
-template <bool BF16, int PPL, bool FULL>
+// LC (LT_CK_GEOM): the chunk length as a compile-time constant, for V = 32
+// (FULL) and fp32 only, where the LDS budget admits L = 5 .. 8: the frame size, the
+// staging's DMA count and the carve's first regions (which depend on L, FB
+// and CP alone) are then immediates. LC = 0: every one of them from the
+// arguments, as for V < 32. ck_kernel_c picks the instantiation of the
+// plan's L and the run-time kernel for any other.
+template <bool BF16, int PPL, bool FULL, int LC = 0>
 __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kernel(const CkArgs a) {
+  static_assert(LC == 0 || FULL, "a compile-time chunk length needs V = 32");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  constexpr int kFbC = 33 * 33 * (BF16 ? 2 : 4);
+  constexpr int kNiC = ((LC * kFbC + 30) / 16 + 63) / 64;  // as ck_plan's c_bytes
+  constexpr int kAdC = kNiC * 1024, kBdC = kAdC + ((4 * LC * 36 + 15) & ~15);
+  const int cL = LC ? LC : a.L;
+  const long long cFB = LC ? (long long)kFbC : a.FB;
+  const int cNi = LC ? kNiC : a.c_ni;
+  const int cOffAd = LC ? kAdC : a.c_off_ad, cOffBd = LC ? kBdC : a.c_off_bd;
   if (a.cont && (int)blockIdx.x < a.B) {  // phase 2 of utterance blockIdx.x's walks
     CK_STAMP(0);
     if (LT_CK_WPRIO) __builtin_amdgcn_s_setprio(LT_CK_WPRIO);
@@ -1574,11 +1631,11 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
   if (a.uflag[b]) return;  // the frame-serial kernels own this utterance
   int nf = a.nfr[b];
   nf = nf < 0 ? 0 : (nf > a.T ? a.T : nf);
-  const int Kl = (nf + a.L - 1) / a.L, Kh = Kl / 2;
+  const int Kl = (nf + cL - 1) / cL, Kh = Kl / 2;
   const int k = j < 2 * Kh ? ((j & 1) ? Kh - 1 - (j >> 1) : Kh + (j >> 1)) : j;
-  const int t0 = k * a.L;
-  const int tend = min(t0 + a.L, a.T);
-  const int t1 = max(t0, min(t0 + a.L, nf));
+  const int t0 = k * cL;
+  const int tend = min(t0 + cL, a.T);
+  const int t1 = max(t0, min(t0 + cL, nf));
   // FULL: V = 32, every stride a compile-time constant
   const int V = FULL ? 32 : a.V, C = V + 1, R = V + 1, FR = C * R, CP = FULL ? 36 : a.CP;
   const int NPG = a.NPG, NP = a.NP;
@@ -1619,15 +1676,15 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
   // stage the chunk's live frames
   const long long off = e0 * (BF16 ? 2 : 4);
   if (!split) {
-    dma_issue(a.W, off, (long long)nt * a.FB, lds_base_addr(lds), a.c_ni, lane, wave, kMargWaves);
+    dma_issue(a.W, off, (long long)nt * cFB, lds_base_addr(lds), cNi, lane, wave, kMargWaves);
   } else if (role < 2) {
-    const int n1 = (int)(((off & 15) + (long long)hs * a.FB + 1023) >> 10);
-    dma_range(a.W, off, (long long)nt * a.FB, lds_base_addr(lds), role == 0 ? 0 : max(n1 - 1, 0),
-              role == 0 ? n1 : a.c_ni, lane);
+    const int n1 = (int)(((off & 15) + (long long)hs * cFB + 1023) >> 10);
+    dma_range(a.W, off, (long long)nt * cFB, lds_base_addr(lds), role == 0 ? 0 : max(n1 - 1, 0),
+              role == 0 ? n1 : cNi, lane);
   }
   unsigned char* wch = lds + (off & 15);
-  float* xa = (float*)(lds + a.c_off_ad);  // [L][CP] alpha_f, linear, max 1 (scale fs Ma)
-  float* xb = (float*)(lds + a.c_off_bd);  // [L][CP] beta_{f+1} of the core, linear, max 1
+  float* xa = (float*)(lds + cOffAd);  // [L][CP] alpha_f, linear, max 1 (scale fs Ma)
+  float* xb = (float*)(lds + cOffBd);  // [L][CP] beta_{f+1} of the core, linear, max 1
   float* an = (float*)(lds + a.c_off_an);  // [L][NPG] numerator alpha_f (log2)
   float* bn = (float*)(lds + a.c_off_bn);  // [L][NPG] numerator beta_{f+1} (log2)
   float2* nw = (float2*)(lds + a.c_off_nw);  // [L][NPG] (blank of u, arc into u), log2
@@ -1638,8 +1695,8 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
   float* buf = (float*)(lds + a.c_off_buf) + 64 * wave;
   float* cfl = (float*)(lds + a.c_off_cf);
   int* fl = (int*)(lds + a.c_off_fl);
-  int* ford = fl + a.L;
-  int* njob = ford + a.L;
+  int* ford = fl + cL;
+  int* njob = ford + cL;
   int* cert_fail = njob + 1;  // a frame outside the certificate (any wave)
   // per-frame progress bits for the marginal pass (kFl*), the frames in
   // the order their inputs complete (middle first), a job counter
@@ -1696,7 +1753,7 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
     }
     if (!kNoAcq) acquire_agent();
     CK_STAMP(6);
-    fl[2 * a.L + 2] = ok;
+    fl[2 * cL + 2] = ok;
   }
   if (!split) {
     gather_tables(a, b, labs, boff, loff, tid, blockDim.x);
@@ -1707,7 +1764,7 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
   }
-  if (a.cont && !fl[2 * a.L + 2]) {
+  if (a.cont && !fl[2 * cL + 2]) {
     if (tid == 0) a.uflag[b] = 1;
     return;
   }
@@ -1720,9 +1777,9 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
   // frames as E once that frame's bit is set. No pass and barrier of its
   // own, one exponential per element. The marginals read E_f and leave the
   // frame's dW in its place.
-  auto wrow = [&](int f) -> const unsigned char* { return wch + f * a.FB; };
+  auto wrow = [&](int f) -> const unsigned char* { return wch + f * cFB; };
   auto eptr = [&](int f) -> float* {
-    return BF16 ? (float*)(lds + a.c_off_e) + f * FRP : (float*)(wch + f * a.FB);
+    return BF16 ? (float*)(lds + a.c_off_e) + f * FRP : (float*)(wch + f * cFB);
   };
   auto ew = [](float w, float cl) -> float {
     return __builtin_amdgcn_exp2f(__builtin_fmaf(w, kLog2e, -cl));
@@ -1740,7 +1797,7 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
     const int uc = min(u, NPG - 1);
     const int ob = boff[uc], ol = max(loff[uc], 0);
     const bool inb = u < NP, inl = u >= 1 && u < NP;
-    const int FBi = (int)a.FB;
+    const int FBi = (int)cFB;
     float2 g2[NU];
 #pragma unroll
     for (int i = 0; i < NU; ++i) {
@@ -1765,14 +1822,14 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
     for (int i = 0; i < 4; ++i) {
       const int x = min(tid + 64 * kMargWaves * i, nnw - 1);
       const int f = x / NPG, u = x - f * NPG;
-      const unsigned char* fr = wch + f * a.FB;
+      const unsigned char* fr = wch + f * cFB;
       const int lo = loff[u];
       const float wb = ldsw<BF16>(fr, boff[u]), wl = ldsw<BF16>(fr, max(lo, 0));
       g2[i] = make_float2(u < NP ? wb * kLog2e : -kInf, (u >= 1 && u < NP) ? wl * kLog2e : -kInf);
     }
     for (int x = tid + 4 * 64 * kMargWaves; x < nnw; x += 64 * kMargWaves) {  // long strings
       const int f = x / NPG, u = x - f * NPG;
-      const unsigned char* fr = wch + f * a.FB;
+      const unsigned char* fr = wch + f * cFB;
       const int lo = loff[u];
       const float wb = ldsw<BF16>(fr, boff[u]), wl = ldsw<BF16>(fr, max(lo, 0));
       nw[x] = make_float2(u < NP ? wb * kLog2e : -kInf, (u >= 1 && u < NP) ? wl * kLog2e : -kInf);
@@ -1782,7 +1839,7 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
       if (tid + 64 * kMargWaves * i < nnw) nw[tid + 64 * kMargWaves * i] = g2[i];
   }
   if (!split) {
-    if (tid < nt) fs[tid * kFs + kFsW00] = ldsw<BF16>(wch + tid * a.FB, 0) * kLog2e;
+    if (tid < nt) fs[tid * kFs + kFsW00] = ldsw<BF16>(wch + tid * cFB, 0) * kLog2e;
     init_flags(tid);
     __syncthreads();  // nw, fs, fl and the job order for every wave
   }
@@ -1894,11 +1951,22 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
       // xa = alpha_f over 2^Ma (the marginals' row) and the step's operand
       // row buf (36 floats, 0 past V)
       const float xv = lane == 0 ? __builtin_amdgcn_exp2f(a0 - Ma) : al * __builtin_amdgcn_exp2f(S - Ma);
+      if constexpr (kPredSt) {
+        // two unconditional stores, no exec-mask cluster: lanes 36 / 37 of the
+        // first carry the (wave-uniform) Ma / a0 to fs, the lanes past it land
+        // in the row's unused slots [36, 64); the lanes past C of the second
+        // land there too
+        float* p0 = lane == 36 ? fs + f * kFs + kFsMa : lane == 37 ? fs + f * kFs + kFsA0 : buf + lane;
+        *p0 = lane == 36 ? Ma : lane == 37 ? a0 : xv;
+        float* p1 = lane < C ? xa + f * CP + lane : buf + 36 + (lane & 15);
+        *p1 = xv;
+      } else {
       if (lane < 36) buf[lane] = xv;
       if (lane < C) xa[f * CP + lane] = xv;
       if (lane == 0) {
         fs[f * kFs + kFsMa] = Ma;
         fs[f * kFs + kFsA0] = a0;
+      }
       }
       // LT_CK_EPIPE: the next frame's E under this step's LDS round trip
       // (a wave issues in order: fetched at the top of the next step, its
@@ -1992,11 +2060,21 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
       const float Mb = mc > 0.f ? S + (float)ex : S;
       const float xv = be * __builtin_amdgcn_exp2f(S - Mb);  // <= 1
       // buf[y-1] = xb[y] for core y; 0 past V
+      if constexpr (kPredSt) {
+        // as alpha's: lanes 33 / 34 carry Mb / b0, lane 0 and the lanes past
+        // 34 land in the row's unused slots [32, 64)
+        float* p0 = lane == 33 ? fs + f * kFs + kFsMb : lane == 34 ? fs + f * kFs + kFsB0
+                  : (lane >= 1 && lane <= 32) ? buf + lane - 1 : buf + 32 + (lane & 31);
+        *p0 = lane == 33 ? Mb : lane == 34 ? b0 : xv;
+        float* p1 = lane < C ? xb + f * CP + lane : buf + 32 + (lane & 31);
+        *p1 = xv;
+      } else {
       if (lane >= 1 && lane <= 32) buf[lane - 1] = xv;
       if (lane < C) xb[f * CP + lane] = xv;
       if (lane == 0) {
         fs[f * kFs + kFsMb] = Mb;
         fs[f * kFs + kFsB0] = b0;
+      }
       }
       float en[16], enb = 0.f, en0y = 0.f, wn00 = 0.f;
       if (kEpipe && f - 1 >= hs) get_e(f - 1, en, enb, en0y, wn00);
@@ -2074,12 +2152,12 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
         const int j2 = c2 / a.B, b2 = c2 - j2 * a.B;
         int nf2 = a.nfr[b2];
         nf2 = nf2 < 0 ? 0 : (nf2 > a.T ? a.T : nf2);
-        const int Kl2 = (nf2 + a.L - 1) / a.L, Kh2 = Kl2 / 2;
+        const int Kl2 = (nf2 + cL - 1) / cL, Kh2 = Kl2 / 2;
         const int k2 = j2 < 2 * Kh2 ? ((j2 & 1) ? Kh2 - 1 - (j2 >> 1) : Kh2 + (j2 >> 1)) : j2;
-        const int t02 = k2 * a.L, t12 = max(t02, min(t02 + a.L, nf2));
+        const int t02 = k2 * cL, t12 = max(t02, min(t02 + cL, nf2));
         if (t12 > t02)
           pf_lines(a.W, ((long long)b2 * a.T + t02) * FR * (BF16 ? 2 : 4),
-                   (long long)(t12 - t02) * a.FB, lds_base_addr((unsigned char*)buf), lane);
+                   (long long)(t12 - t02) * cFB, lds_base_addr((unsigned char*)buf), lane);
       }
     }
     for (int f = nt - 1; f >= 0; --f) {
@@ -2335,7 +2413,7 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
     if constexpr (BF16) {  // the frame's dW, rounded once, over its own W bytes
-      unsigned short* fo = (unsigned short*)(wch + f * a.FB);
+      unsigned short* fo = (unsigned short*)(wch + f * cFB);
       for (int e = lane; e < FR; e += 64) fo[e] = f2bf(fb[e]);
     }
   }
@@ -2349,7 +2427,7 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
   CK_STAMP(3);
   {
     const long long es = BF16 ? 2 : 4;
-    const long long bytes = (long long)nt * a.FB;
+    const long long bytes = (long long)nt * cFB;
     unsigned char* gdst = (unsigned char*)a.dW + off;  // same byte offset as W
     const long long head = min((long long)((16 - (off & 15)) & 15), bytes);
     const long long body = (bytes - head) & ~15LL;
@@ -2602,7 +2680,37 @@ int ck_launch_ab(CkArgs& a, bool bf16, hipStream_t st) {
   if (rc || fuse) return rc;
   return ck_launch(ck_kernel_b(a.PPL), a.B, kWalkLdsBytes, st, a);
 }
-const void* ck_kernel_c(int ppl, bool bf16, bool full) {
+// the V = 32 instantiation of chunk length L (LT_CK_GEOM), or nullptr
+// (fp32 only: for bf16 W the instantiations measured no gain, or a loss, and
+// spill more SGPRs than the run-time kernel, so bf16 keeps the run-time kernel)
+template <int LC>
+const void* ck_kernel_c_len(int ppl) {
+  return ppl == 1 ? (const void*)ck_marg_kernel<false, 1, true, LC>
+                  : (const void*)ck_marg_kernel<false, 2, true, LC>;
+}
+// the chunk length of the instantiation the last phase C launch took (0: the
+// run-time kernel); the diagnostic build exports it for the tests
+int g_last_marg_len = 0;
+// LT_CHUNK_GENERIC=1 (read per call): the run-time-geometry kernel whatever
+// the plan (tests compare the two bit for bit)
+const void* ck_kernel_c(int ppl, bool bf16, bool full, const CkArgs& a) {
+  g_last_marg_len = 0;
+  if (kGeom && full && !bf16 && ck_env("LT_CHUNK_GENERIC", 0) == 0) {
+    // the instantiation must be the plan's: L, and the carve it implies
+    const int fb = 33 * 33 * (bf16 ? 2 : 4);
+    const int ni = ((a.L * fb + 30) / 16 + 63) / 64;
+    const bool match = a.FB == fb && a.CP == 36 && a.c_ni == ni && a.c_off_ad == ni * 1024 &&
+                       a.c_off_bd == ni * 1024 + al16(4LL * a.L * 36);
+    if (match && a.L >= 5 && a.L <= 8) {
+      g_last_marg_len = a.L;
+      switch (a.L) {
+        case 5: return ck_kernel_c_len<5>(ppl);
+        case 6: return ck_kernel_c_len<6>(ppl);
+        case 7: return ck_kernel_c_len<7>(ppl);
+        default: return ck_kernel_c_len<8>(ppl);
+      }
+    }
+  }
   if (full)
     return ppl == 1 ? (bf16 ? (const void*)ck_marg_kernel<true, 1, true>
                             : (const void*)ck_marg_kernel<false, 1, true>)
@@ -2623,6 +2731,11 @@ int ck_lds_c(const CkArgs& a, bool bf16) {
 }
 
 }  // namespace
+
+#ifdef LT_DIAG
+// diagnostic build only: which ck_marg_kernel the last chunked call launched
+extern "C" int lt_diag_chunk_marg_len(void) { return g_last_marg_len; }
+#endif
 
 namespace lt_impl {
 bool chunk_eligible(const lt_problem* pb) {
@@ -2680,7 +2793,7 @@ int chunk_loss_grad(const lt_problem* pb, int local_norm, const void* W, const i
   a.half = 1;
   if ((rc = ck_launch_ab(a, bf16, st))) return rc;
   a.cont = 1;
-  if ((rc = ck_launch(ck_kernel_c(a.PPL, bf16, a.V == 32), a.B + a.B * a.K,
+  if ((rc = ck_launch(ck_kernel_c(a.PPL, bf16, a.V == 32, a), a.B + a.B * a.K,
                       std::max(ck_lds_c(a, bf16), kWalkLdsBytes), st, a, 64 * kMargWaves)))
     return rc;
   char* sc = (char*)scratch;
@@ -2764,7 +2877,7 @@ int lt_chunk_backward(const lt_problem* pb, int32_t local_norm, const void* W,
   a.dW = dW;
   hipStream_t st = (hipStream_t)stream;
   const bool bf16 = pb->weight_dtype == LT_DTYPE_BF16;
-  if ((rc = ck_launch(ck_kernel_c(a.PPL, bf16, a.V == 32), a.B * a.K, ck_lds_c(a, bf16), st, a,
+  if ((rc = ck_launch(ck_kernel_c(a.PPL, bf16, a.V == 32, a), a.B * a.K, ck_lds_c(a, bf16), st, a,
                       64 * kMargWaves)))
     return rc;
   char* sc = (char*)scratch;

@@ -266,29 +266,44 @@ LT_DPP_OP(dpp_max, "v_max_f32_dpp")
 LT_DPP_OP(dpp_add, "v_add_f32_dpp")
 #undef LT_DPP_OP
 
-// max / sum over lanes 8k+7 (k = 0..7) of the wave, returned wave-uniform;
-// every other lane must hold the identity. row_shr:8 folds lane 7 into 15
-// of each row, row_bcast:15 rows 0/2 into 1/3, row_bcast:31 rows 0-1 into
-// 2-3; lane 63 ends with the total.
+// The last two stages of a wave reduction over rows that each hold their own
+// total in lane 15 (of the row): row_bcast:15 folds rows 0/2 into 1/3,
+// row_bcast:31 rows 0-1 into 2-3, and lane 63 of the result holds the total.
+// Each fold writes only the rows of its row_mask, so every other lane of the
+// result is undefined: read lane 63 alone. v_max_f32 here has no
+// canonicalising pre-op: a quiet NaN operand is dropped as fmaxf drops it, a
+// signalling NaN (which no arithmetic produces) comes back quieted.
 template <bool MAX>
-LT_DEVINL float xlane_reduce(float v) {
-  float r1, r2, r3;
+LT_DEVINL float rows_fold(float v) {
+  float r2, r3;
   if constexpr (MAX) {
-    asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_shr:8 row_mask:0xf bank_mask:0xf"
-        : "=v"(r1) : "v"(v));
     asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_bcast:15 row_mask:0xa bank_mask:0xf"
-        : "=v"(r2) : "v"(r1));
+        : "=v"(r2) : "v"(v));
     asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_bcast:31 row_mask:0xc bank_mask:0xf"
         : "=v"(r3) : "v"(r2));
   } else {
-    asm("s_nop 1\n\tv_add_f32_dpp %0, %1, %1 row_shr:8 row_mask:0xf bank_mask:0xf"
-        : "=v"(r1) : "v"(v));
     asm("s_nop 1\n\tv_add_f32_dpp %0, %1, %1 row_bcast:15 row_mask:0xa bank_mask:0xf"
-        : "=v"(r2) : "v"(r1));
+        : "=v"(r2) : "v"(v));
     asm("s_nop 1\n\tv_add_f32_dpp %0, %1, %1 row_bcast:31 row_mask:0xc bank_mask:0xf"
         : "=v"(r3) : "v"(r2));
   }
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(r3), 63));
+  return r3;
+}
+
+// max / sum over lanes 8k+7 (k = 0..7) of the wave, returned wave-uniform;
+// every other lane must hold the identity. row_shr:8 folds lane 7 into 15
+// of each row, rows_fold the rows; lane 63 ends with the total.
+template <bool MAX>
+LT_DEVINL float xlane_reduce(float v) {
+  float r1;
+  if constexpr (MAX) {
+    asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_shr:8 row_mask:0xf bank_mask:0xf"
+        : "=v"(r1) : "v"(v));
+  } else {
+    asm("s_nop 1\n\tv_add_f32_dpp %0, %1, %1 row_shr:8 row_mask:0xf bank_mask:0xf"
+        : "=v"(r1) : "v"(v));
+  }
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rows_fold<MAX>(r1)), 63));
 }
 
 LT_DEVINL float grp_max(float v, int lg) {

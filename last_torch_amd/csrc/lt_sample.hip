@@ -99,18 +99,13 @@ struct Pick {
 };
 
 // max over the wave, wave-uniform: four butterfly stages inside each DPP row,
-// row_bcast:15 / :31 across the rows, lane 63 read back (xlane_reduce's tail).
+// rows_fold across the rows, lane 63 read back.
 LT_DEVINL float wave_max(float v) {
   v = dpp_max<0>(v);
   v = dpp_max<1>(v);
   v = dpp_max<2>(v);
   v = dpp_max<3>(v);
-  float r2, r3;
-  asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_bcast:15 row_mask:0xa bank_mask:0xf"
-      : "=v"(r2) : "v"(v));
-  asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_bcast:31 row_mask:0xc bank_mask:0xf"
-      : "=v"(r3) : "v"(r2));
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(r3), 63));
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rows_fold<true>(v)), 63));
 }
 
 // Folds one slice of at most 64 candidates (lane: ok, arc k from state p, in
