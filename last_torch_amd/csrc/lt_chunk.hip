@@ -22,22 +22,29 @@
 //      P_k = M_{t0} ... M_{t1-1} in scaled linear space. The 32 x 32 core
 //      product runs on the matrix cores (v_mfma_f32_32x32x2_f32: exact f32
 //      FMA chains) as X <- E_t^T X with X = P^T, one column scale per start
-//      state; the state-0 row and the state-0 self loop on the side. Also
-//      the numerator's group bands (the string lattice's frame steps
-//      composed over kGrp frames) and the frame offsets.
+//      state; the state-0 row and the state-0 self loop on the side. The
+//      frames reach the wave through its own two-slot LDS ring (LDS-DMA, a
+//      frame issued two steps ahead). Also the numerator's group bands (the
+//      string lattice's frame steps composed over kGrp frames, a step of
+//      their own beside the frame's product) and the frame offsets.
 //   B  one workgroup per utterance: the den alpha / beta vectors at every
 //      chunk boundary (K steps of a 33 x 33 log-semiring vector-matrix
 //      product each), the numerator alpha / beta over the groups with the
 //      values at the chunk boundaries kept; log_z, num, loss.
 //      A and B share ck_ab_kernel: the walks follow A's chunks through
-//      per-chunk ready flags (write-through stores, agent-scope acquire), so
-//      they run beside the transfers instead of after them (B > CUs or
-//      LT_CHUNK_FUSE=0: ck_combine_kernel after the launch).
+//      per-chunk ready flags (write-through stores, L1-bypassing sc1 loads,
+//      no acquire), so they run beside the transfers instead of after them
+//      (B > CUs or LT_CHUNK_FUSE=0: ck_combine_kernel after the launch).
 //   C  ck_marg_kernel      one workgroup per chunk: the chunk's W staged in
-//      LDS once; local den / num alpha and beta recursions from the
-//      boundary values (four waves side by side), then the arc marginals of
-//      every frame, normalised by the frame's own total (= Z up to
-//      rounding), den minus num, times the incoming gradient -> dW.
+//      LDS once by all four waves; local den / num alpha and beta recursions
+//      from the boundary values (four waves side by side, the roles rotating
+//      over the waves by workgroup, the den chains at raised priority), then
+//      the arc marginals of every frame, normalised by the frame's own total
+//      (= Z up to rounding), den minus num, times the incoming gradient ->
+//      dW. For V = 32 and fp32 W the kernel is instantiated per chunk length
+//      (5 .. 8); every other case takes the run-time-geometry kernel.
+// The experiments that led here (split staging, an E pipeline, register
+// prefetch in A, ...) are indexed in profiles/chunk_switches_retired.txt.
 // HBM traffic: W is read twice (A and C) and dW written once, plus G and the
 // chunk records (~10 % of W) -- the SURVEY 8(d) accounting.
 //
@@ -69,105 +76,16 @@ constexpr int kChunkLds = 40 * 1024;  // phase C LDS per workgroup (four per CU)
 constexpr int kMargWaves = 4;   // phase C: waves per workgroup (recursions on 0-3)
 constexpr int kGrp = 7;         // frames per numerator group (band offsets 0..kGrp)
 constexpr float kCert = 64.f;   // phase C's per-frame certificate: log2(max alpha max beta e^c / Z)
-#ifndef LT_AB_WAVES
-#define LT_AB_WAVES 3
-#endif
-constexpr int kAbWaves = LT_AB_WAVES;  // ck_ab_kernel: waves per SIMD its registers allow
-#ifndef LT_CK_APF
-#define LT_CK_APF 1
-#endif
-constexpr int kApf = LT_CK_APF;  // phase A: frames in registers ahead (1 or 2)
-static_assert(kApf == 1 || kApf == 2, "phase A prefetch depth");
-constexpr unsigned kSpinMax = 1u << 20;
-#ifndef LT_CK_SPLIT
-#define LT_CK_SPLIT 0
-#endif
-#ifndef LT_CK_WPRIO
-#define LT_CK_WPRIO 3
-#endif
-#ifndef LT_CK_PRIO
-#define LT_CK_PRIO 3
-#endif
-#ifndef LT_CK_ROT
-#define LT_CK_ROT 1
-#endif
-#ifndef LT_CK_PF
-#define LT_CK_PF 0
-#endif
-// LT_CK_NOACQ: what one launch's workgroups hand each other (the records
-// and bands phase A publishes for the phase-1 walks; the boundary rows the
-// phase-2 walks publish for phase C) is read with sc1 loads, which bypass the
-// reading CU's L1, instead of plain loads behind an agent-scope acquire
-// (buffer_inv sc1: an L1 invalidation per poll, ~1.7 us and more with four
-// workgroups on the CU, MI355X_MICROARCH.md)
-#ifndef LT_CK_NOACQ
-#define LT_CK_NOACQ 1
-#endif
-constexpr bool kNoAcq = LT_CK_NOACQ != 0;
-#ifndef LT_CK_ALDS
-#define LT_CK_ALDS 1
-#endif
-constexpr bool kALds = LT_CK_ALDS != 0;  // phase A: frames through an LDS ring (two slots a wave)
-constexpr int kASlot = 5 * 1024;         // bytes per slot (a fp32 bigram frame: 5 DMA instructions)
-constexpr int kALdsBytes = 4 * 2 * kASlot;  // dynamic LDS of phase A's workgroups
-#ifndef LT_CK_BANDMIX
-#define LT_CK_BANDMIX 0
-#endif
-constexpr bool kBandMix = LT_CK_BANDMIX != 0;  // phase A: band steps between the MFMAs
-#ifndef LT_CK_EPIPE
-#define LT_CK_EPIPE 0
-#endif
-constexpr bool kEpipe = LT_CK_EPIPE != 0;  // phase C den chains: the next frame's E a step ahead
-// phase C's serial path per workgroup (each switch on its own, for A/B runs):
-// LT_CK_NTERM: the numerator's marginal terms by the numerator waves as soon
-// as their chains end, not inside the frame's marginal job: 2 for the last
-// two jobs' frames (the ones the den chains' waves take when they end), 1
-// for every frame (measured slower: waves off the den chains are issue-bound
-// beside the other workgroups' prioritised chains, and this piles the
-// numerator work of all frames on two of them);
-// LT_CK_DENCOL: the marginal job's den pass over columns 1..V (+ the blank
-// column by lane), 2: xa by 16-byte loads where V = 32, 1: by dwords;
-// LT_CK_GSHIFT: the numerator-arc gather maps threads to (frame, position)
-// by shifts, no division
-#ifndef LT_CK_NTERM
-#define LT_CK_NTERM 2
-#endif
-constexpr int kNTerm = LT_CK_NTERM;
-#ifndef LT_CK_DENCOL
-#define LT_CK_DENCOL 2
-#endif
-constexpr int kDenCol = LT_CK_DENCOL;
-#ifndef LT_CK_GSHIFT
-#define LT_CK_GSHIFT 1
-#endif
-constexpr bool kGShift = LT_CK_GSHIFT != 0;
-// LT_CK_DPPRED: the wave reductions (wmax_u / wsum_u) with one DPP-modified
-// v_max_f32 / v_add_f32 per stage (see wred)
-#ifndef LT_CK_DPPRED
-#define LT_CK_DPPRED 1
-#endif
-constexpr bool kDppRed = LT_CK_DPPRED != 0;
-// LT_CK_GEOM: ck_marg_kernel instantiated per chunk length for V = 32 (see
-// the kernel); LT_CHUNK_GENERIC=1 forces the run-time kernel per call
-#ifndef LT_CK_GEOM
-#define LT_CK_GEOM 1
-#endif
-constexpr bool kGeom = LT_CK_GEOM != 0;
-// LT_CK_PREDST: the den steps' single-lane and partial-wave LDS stores as
-// unconditional stores with the address (and value) selected per lane, the
-// idle lanes landing in unused slots of the wave's own buf row. Off: measured
-// no gain alone (-0.2 us of 310, profiles/chunk_issue_diet.txt), same bits
-#ifndef LT_CK_PREDST
-#define LT_CK_PREDST 0
-#endif
-constexpr bool kPredSt = LT_CK_PREDST != 0;
-#ifndef LT_WALK_SLOTS
-#define LT_WALK_SLOTS 3
-#endif
-constexpr int kWalkSlots = LT_WALK_SLOTS;        // phase B: den walk record ring depth (LDS)
+constexpr int kAbWaves = 3;     // ck_ab_kernel: waves per SIMD its registers allow
+constexpr unsigned kSpinMax = 1u << 20;  // the hand-offs' bound on polls without progress (~1 s)
+constexpr int kWalkPrio = 3;    // s_setprio of the walk workgroups (profiles/r05_chunk_prio_ab.txt)
+constexpr int kDenPrio = 3;     // s_setprio of phase C's den chains (profiles/r05_chunk_prio_ab.txt)
+constexpr int kASlot = 5 * 1024;         // phase A: bytes per frame ring slot (a fp32 bigram frame: 5 DMA instructions)
+constexpr int kALdsBytes = 4 * 2 * kASlot;  // dynamic LDS of phase A's workgroups (two slots a wave)
+constexpr int kWalkSlots = 3;                    // phase B: den walk record ring depth in LDS
 constexpr int kRecNi = (4 * kRec + 1023) / 1024;  // LDS-DMA wave instructions per record
 constexpr int kWalkSlot = kRecNi * 1024;         // bytes per ring slot
-constexpr int kWalkLds = 2 * kWalkSlots * kWalkSlot;  // dynamic LDS of the walk launches  // phase B's bound on polls without progress (~1 s)
+constexpr int kWalkLds = 2 * kWalkSlots * kWalkSlot;  // dynamic LDS of the walk launches
 // record layout (floats): [0, 1152) X^T rows: rec[i * 36 + j] = X[i][j] =
 // P_scaled[j][i] (start core state j -> end core state i); [1152, 1184)
 // per-start-state (column) power-of-two scales ej (int); [1184, 1216) the
@@ -216,7 +134,6 @@ struct CkArgs {
   int strict;              // 1 (lt_chunk_forward): a chunk outside the strict range (flag 3)
                            // leaves the fast path in B; 0: phase C's certificate decides
   int dbg;                 // diagnostic builds (LT_DIAG) only: role ablations
-  int pf;                  // phase C: prefetch distance in blocks (0: none), LT_CK_PF
   long long* stamps;       // diagnostic builds only: per-workgroup s_memtime marks
   long long FB;            // bytes per frame
   // phase A per-wave LDS carve
@@ -233,14 +150,9 @@ LT_DEVINL float half_sum(float v) {
   auto p = __builtin_amdgcn_permlane32_swap(__float_as_int(v), __float_as_int(v), false, false);
   return __int_as_float(p[0]) + __int_as_float(p[1]);
 }
-// lane l ^ 32's value
-LT_DEVINL float half_other(float v) {
-  auto p = __builtin_amdgcn_permlane32_swap(__float_as_int(v), __float_as_int(v), false, false);
-  return (threadIdx.x & 32) ? __int_as_float(p[0]) : __int_as_float(p[1]);
-}
-// max of lanes l and l ^ 32 in both (LT_CK_DPPRED: one v_max_f32 on the
-// swap's two results, no select of the other half's and no canonicalising
-// of the operands; a quiet NaN operand is dropped as fmaxf drops it)
+// max of lanes l and l ^ 32 in both: one v_max_f32 on the swap's two
+// results, no select of the other half's and no canonicalising of the
+// operands; a quiet NaN operand is dropped as fmaxf drops it
 LT_DEVINL float half_max(float v) {
   auto p = __builtin_amdgcn_permlane32_swap(__float_as_int(v), __float_as_int(v), false, false);
   float r;
@@ -331,74 +243,21 @@ LT_DEVINL void dma_issue(const unsigned char* base, long long off, long long byt
   }
 }
 
-// One LDS-DMA dword per 128-byte line of [off, off + bytes) of `base`, every
-// lane's dword landing in the same 256-byte LDS scratch (discarded): the
-// lines come into the XCD's L2 (and the memory-side cache) for a block that
-// will stage them later. 8 KiB of lines per wave instruction.
-LT_DEVINL void pf_lines(const unsigned char* base, long long off, long long bytes,
-                        unsigned lds_addr, int lane) {
-  const long long a0 = off & ~127LL;
-  const int nl = (int)((off + bytes - a0 + 127) >> 7);
-  lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-  for (int i = 0; 64 * i < nl; ++i) {
-    const int g = min(lane + 64 * i, nl - 1);
-    const void* src = base + a0 + 128LL * g;
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dword %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(src), "s"(lds_addr)
-        : "memory");
-  }
-}
-
-// dma_issue's copy, wave instructions [i0, i1) only (one wave)
-LT_DEVINL void dma_range(const unsigned char* base, long long off, long long bytes,
-                         unsigned lds_addr, int i0, int i1, int lane) {
-  const long long a0 = off & ~15LL;
-  const int n16 = (int)((off + bytes - a0 + 15) >> 4);
-  for (int i = i0; i < i1; ++i) {
-    int g = lane + 64 * i;
-    g = g < n16 ? g : n16 - 1;
-    glds16(base + a0 + 16LL * g, lds_addr + 1024u * i);
-  }
-}
-
 // wave-uniform max / sum over all 64 lanes with DPP only (no LDS round trip):
 // butterflies inside each row of 16, then row_bcast:15 / row_bcast:31 fold
-// rows 0-1 into 2-3, and lane 63 holds the total
-// LT_CK_DPPRED: every stage as one v_max_f32 / v_add_f32 with a DPP source
-// operand (dpp_max / dpp_add, then rows_fold) in place of v_mov_dpp + two
-// canonicalising v_max + the op. Same stages in the same order, the total
-// in lane 63. Without the canonicalising pre-ops v_max_f32 drops a quiet NaN
-// operand as fmaxf does but returns a signalling NaN quieted: the callers'
-// values come out of arithmetic (or, in phase A's frame max, out of
-// max3_raw, which never quieted either), so no signalling NaN reaches it
-// unless W itself holds one, and that W fails phase A's e >= 0 test as any
-// NaN does.
+// rows 0-1 into 2-3, and lane 63 holds the total. Every stage is one
+// v_max_f32 / v_add_f32 with a DPP source operand (dpp_max / dpp_add, then
+// rows_fold), not v_mov_dpp + two canonicalising v_max + the op. Without the
+// canonicalising pre-ops v_max_f32 drops a quiet NaN operand as fmaxf does
+// but returns a signalling NaN quieted: the callers' values come out of
+// arithmetic (or, in phase A's frame max, out of max3_raw, which never
+// quieted either), so no signalling NaN reaches it unless W itself holds
+// one, and that W fails phase A's e >= 0 test as any NaN does.
 template <bool MAX>
 LT_DEVINL float wred(float v) {
-  if constexpr (kDppRed) {
-    if constexpr (MAX) v = dpp_max<3>(dpp_max<2>(dpp_max<1>(dpp_max<0>(v))));
-    else v = dpp_add<3>(dpp_add<2>(dpp_add<1>(dpp_add<0>(v))));
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rows_fold<MAX>(v)), 63));
-  }
-  auto op = [](float x, float y) { return MAX ? fmaxf(x, y) : x + y; };
-  v = op(v, xchg<0>(v));
-  v = op(v, xchg<1>(v));
-  v = op(v, xchg<2>(v));
-  v = op(v, xchg<3>(v));
-  const float r15 = __int_as_float(__builtin_amdgcn_update_dpp(
-      MAX ? __float_as_int(v) : 0, __float_as_int(v), 0x142, 0xA, 0xF, false));
-  v = op(v, r15);
-  const float r31 = __int_as_float(__builtin_amdgcn_update_dpp(
-      MAX ? __float_as_int(v) : 0, __float_as_int(v), 0x143, 0xC, 0xF, false));
-  v = op(v, r31);
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+  if constexpr (MAX) v = dpp_max<3>(dpp_max<2>(dpp_max<1>(dpp_max<0>(v))));
+  else v = dpp_add<3>(dpp_add<2>(dpp_add<1>(dpp_add<0>(v))));
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rows_fold<MAX>(v)), 63));
 }
 LT_DEVINL float wmax_u(float v) { return wred<true>(v); }
 LT_DEVINL float wsum_u(float v) { return wred<false>(v); }
@@ -448,8 +307,8 @@ LT_DEVINL float lse2_b2(float x, float y) {
 }
 
 // ---------------------------------------------------------------------------
-// A: chunk transfer matrices (one wave per chunk). Frame data is loaded
-// straight into registers two frames ahead (the compiler's own waits).
+// A: chunk transfer matrices (one wave per chunk). The frames come through a
+// two-slot LDS ring per wave (LDS-DMA) and into registers one step ahead.
 // ---------------------------------------------------------------------------
 template <bool BF16, int PPL>
 struct FrameRegs {
@@ -461,10 +320,9 @@ struct FrameRegs {
   float gb[PPL], gl[PPL];  // numerator arc weights of the lane's positions
 };
 
-// Per-lane byte offsets of load_frame's loads inside a frame, fixed over the
-// chunk: the frame is one buffer resource (scalar base, bounded), so a load
-// costs no address arithmetic. The lane's k-step rows sit at compile-time
-// immediates past vb (FULL) or at scalar offsets (srow).
+// Per-lane byte offsets of lds_frame's reads inside a frame, fixed over the
+// chunk. The lane's k-step rows sit at compile-time immediates past vb
+// (FULL) or at scalar offsets (srow).
 template <int PPL>
 struct FrameOffs {
   int vb, vr0, vbl, vdg, vgb[PPL], vgl[PPL];
@@ -487,38 +345,9 @@ LT_DEVINL void frame_offsets(const CkArgs& a, int lane, const int* boff, const i
 #pragma unroll
   for (int s = 0; s < 16; ++s) o.srow[s] = krow(s) * R * es;
 }
-template <bool BF16>
-LT_DEVINL float ldb(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  if constexpr (BF16)
-    return __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, 0) << 16);
-  else
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-// Every lane issues every load (rows and columns past V read neighbouring
-// bytes of the chunk or, past its end, the resource's zeros; mask_frame
-// replaces them): no load sits under a branch, so the compiler's vmcnt
-// bookkeeping across the prefetch stays exact.
-template <bool BF16, int PPL, bool FULL>
-LT_DEVINL void load_frame(const unsigned char* Wf, int bytes, const FrameOffs<PPL>& o,
-                          FrameRegs<BF16, PPL>& f) {
-  const __amdgpu_buffer_rsrc_t r =
-      __builtin_amdgcn_make_buffer_rsrc((void*)Wf, (short)0, bytes, 0x00020000);
-  constexpr int es = BF16 ? 2 : 4;
-#pragma unroll
-  for (int s = 0; s < 16; ++s)
-    f.w[s] = FULL ? ldb<BF16>(r, o.vb + krow(s) * 33 * es, 0) : ldb<BF16>(r, o.vb, o.srow[s]);
-  f.wr0 = ldb<BF16>(r, o.vr0, 0);
-  f.wbl = ldb<BF16>(r, o.vbl, 0);
-  f.wdg = ldb<BF16>(r, o.vdg, 0);
-  f.w00 = ldb<BF16>(r, 0, 0);
-#pragma unroll
-  for (int q = 0; q < PPL; ++q) {
-    f.gb[q] = ldb<BF16>(r, o.vgb[q], 0);
-    f.gl[q] = ldb<BF16>(r, o.vgl[q], 0);
-  }
-}
-// load_frame's values from a frame staged in LDS (LT_CK_ALDS: `fr` = the
-// frame's first byte in the wave's ring slot)
+// The lane's values of a frame staged in LDS (`fr` = the frame's first byte
+// in the wave's ring slot). Every lane issues every read (rows and columns
+// past V read neighbouring bytes of the slot; mask_frame replaces them).
 template <bool BF16, int PPL, bool FULL>
 LT_DEVINL void lds_frame(const unsigned char* fr, const FrameOffs<PPL>& o,
                          FrameRegs<BF16, PPL>& f) {
@@ -539,7 +368,7 @@ LT_DEVINL void lds_frame(const unsigned char* fr, const FrameOffs<PPL>& o,
     f.gl[q] = rd(o.vgl[q]);
   }
 }
-// the values load_frame read for nothing (FULL: V = 32, every core value live)
+// the values lds_frame read for nothing (FULL: V = 32, every core value live)
 template <bool BF16, int PPL, bool FULL>
 LT_DEVINL void mask_frame(int V, int lane, const int* boff, const int* loff,
                           FrameRegs<BF16, PPL>& f) {
@@ -587,7 +416,7 @@ LT_DEVINL void st_wt4(__amdgpu_buffer_rsrc_t r, int idx, float x, float y, float
 // agent-scope flag store (1: inside the strict range; 3: a masked (-inf) or
 // far-below-max weight, which only the relaxed path takes, under phase C's
 // per-frame certificate; 2: a NaN / +inf weight or an all -inf frame, always
-// the frame-serial kernels); phase B polls it and acquires (ChunkReady).
+// the frame-serial kernels); phase B polls it (ChunkReady).
 template <bool BF16, int PPL, bool FULL>
 LT_DEVINL void transfer_role(const CkArgs& a, int b, int k, int wave) {
   __shared__ __attribute__((aligned(16))) float s_rt[4][32];
@@ -622,8 +451,6 @@ LT_DEVINL void transfer_role(const CkArgs& a, int b, int k, int wave) {
     loff[r] = -1;
     if (u < NPG) string_offsets(a, lab, u, &boff[r], &loff[r]);
   }
-  const long long es = BF16 ? 2 : 4;
-  const unsigned char* W0 = a.W + ((long long)b * a.T + t0) * a.FR * es;
   CK_ASTAMP(1);
 
   v16f X;  // X = P^T, column j (lane & 31) = start state j+1; identity
@@ -640,15 +467,14 @@ LT_DEVINL void transfer_role(const CkArgs& a, int b, int k, int wave) {
   float nbd[PPL][kGrp + 1];
   const __amdgpu_buffer_rsrc_t nbr = wt_rsrc(a.nb + (long long)id * a.nbs, 4 * a.nbs);
 
-  // the next frame in registers; the loads are unconditional (clamped to
-  // the chunk's last frame) so the compiler's vmcnt tracking stays exact
+  // the current frame in registers
   FrameRegs<BF16, PPL> fr;
   FrameOffs<PPL> fo;
   frame_offsets<BF16, PPL>(a, lane, boff, loff, fo);
-  // LT_CK_ALDS: this wave's two ring slots in the launch's dynamic LDS
+  // this wave's two ring slots in the launch's dynamic LDS
   extern __shared__ __attribute__((aligned(16))) unsigned char ck_dyn[];
   unsigned char* aring = ck_dyn + wave * 2 * kASlot;
-  float cfl_lane = 0.f;  // LT_CK_ALDS: lane f holds frame f's offset
+  float cfl_lane = 0.f;  // lane f holds frame f's offset
   auto goff = [&](int f) { return ((long long)b * a.T + t0 + f) * a.FB; };
   auto aissue = [&](int f) {
     dma_issue(a.W, goff(f), a.FB, lds_base_addr(aring) + (unsigned)((f & 1) * kASlot), a.a_ni, lane);
@@ -656,31 +482,13 @@ LT_DEVINL void transfer_role(const CkArgs& a, int b, int k, int wave) {
   auto aframe = [&](int f) -> const unsigned char* {
     return aring + (f & 1) * kASlot + (int)(goff(f) & 15);
   };
-  (void)aissue; (void)aframe;
-  auto frame_ptr = [&](int f) { return W0 + (long long)min(f, nt - 1) * a.FR * es; };
-  auto frame_bytes = [&](int f) { return (nt - min(f, nt - 1)) * a.FR * (int)es; };
   auto step = [&](FrameRegs<BF16, PPL>& F, int f, bool reload) {
     mask_frame<BF16, PPL, FULL>(V, lane, boff, loff, F);
     // numerator: band step over the group (positions past the string read -inf)
     // (diagnostic builds: LT_CK_DBG bit 1024 skips it -- timing only)
     const bool bands = !LT_ABL(a, 1024);
-    const int jg = f / kGrp, flg = f - jg * kGrp;  // wave-uniform
-    if (kBandMix && bands) {
-      // LT_CK_BANDMIX: this frame's weights published now (F is reloaded
-      // below); the band steps themselves run between the core product's
-      // MFMAs, which they do not depend on
-#pragma unroll
-      for (int r = 0; r < PPL; ++r)
-        sg[lane + 64 * r] = make_float2(F.gb[r] * kLog2e, F.gl[r] * kLog2e);
-      if (flg == 0) {
-#pragma unroll
-        for (int r = 0; r < PPL; ++r)
-#pragma unroll
-          for (int d = 0; d <= kGrp; ++d) nbd[r][d] = d ? -kInf : 0.f;
-      }
-    }
-    if (!kBandMix && bands) {
-      const int j = jg, fl = flg;
+    const int j = f / kGrp, fl = f - j * kGrp;  // wave-uniform
+    if (bands) {
 #pragma unroll
       for (int r = 0; r < PPL; ++r)
         sg[lane + 64 * r] = make_float2(F.gb[r] * kLog2e, F.gl[r] * kLog2e);
@@ -715,13 +523,11 @@ LT_DEVINL void transfer_role(const CkArgs& a, int b, int k, int wave) {
       }
       __builtin_amdgcn_wave_barrier();
     }
-    if constexpr (kALds) {
-      // frame f + 2 into the slot frame f came through (its reads into F have
-      // returned: F was just used)
-      if (f + 2 < nt && !LT_ABL(a, 8192)) {
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        aissue(f + 2);
-      }
+    // frame f + 2 into the slot frame f came through (its reads into F have
+    // returned: F was just used)
+    if (f + 2 < nt && !LT_ABL(a, 8192)) {
+      __builtin_amdgcn_s_waitcnt(0xc07f);
+      aissue(f + 2);
     }
     // the frame's offset c = ceil(max W log2 e), an integer in log2 units
     // (masked values are -inf), so every sum of offsets is exact
@@ -731,8 +537,7 @@ LT_DEVINL void transfer_role(const CkArgs& a, int b, int k, int wave) {
     mx = wmax_u(mx);
     const bool cfin = __builtin_isfinite(mx);
     const float cl = cfin ? ceilf(mx * kLog2e) : 0.f;
-    if constexpr (kALds) cfl_lane = lane == f ? cl : cfl_lane;  // stored after the frames
-    else if (lane == 0) a.cf[(long long)b * a.T + t0 + f] = cl;
+    cfl_lane = lane == f ? cl : cfl_lane;  // stored after the frames
     // E_t^T as the A operand: lane (i, h), k-step s -> E[k][i]. The core
     // diagonal's blank self loop (alignments.py:294-297) is added beside
     // the product (Dg X after the MFMAs, rt Dg in the state-0 row), which
@@ -772,16 +577,12 @@ LT_DEVINL void transfer_role(const CkArgs& a, int b, int k, int wave) {
     }
     const float w00 = F.w00;
     // (diagnostic builds: bit 8192 keeps the chunk's first frame -- timing only)
-    if constexpr (kALds) {
-      // frame f + 1 from its ring slot: its DMA was issued at the start of
-      // step f - 1; only frame f + 2's (issued at the start of this step)
-      // may still be in flight
-      if (reload && !LT_ABL(a, 8192)) {
-        wait_vmcnt(f + 2 < nt ? a.a_ni : 0);
-        lds_frame<BF16, PPL, FULL>(aframe(f + 1), fo, F);
-      }
-    } else if (reload && !LT_ABL(a, 8192)) {
-      load_frame<BF16, PPL, FULL>(frame_ptr(f + kApf), frame_bytes(f + kApf), fo, F);
+    // frame f + 1 from its ring slot: its DMA was issued at the start of
+    // step f - 1; only frame f + 2's (issued at the start of this step)
+    // may still be in flight
+    if (reload && !LT_ABL(a, 8192)) {
+      wait_vmcnt(f + 2 < nt ? a.a_ni : 0);
+      lds_frame<BF16, PPL, FULL>(aframe(f + 1), fo, F);
     }
 
     // state-0 row: r' = p00 * e0 + r Ec (VALU, beside the MFMAs), scaled by
@@ -814,48 +615,8 @@ LT_DEVINL void transfer_role(const CkArgs& a, int b, int k, int wave) {
     // (diagnostic builds: bit 2048 skips the product and the column scales -- timing only)
     if (LT_ABL(a, 2048)) return;
     v16f D = {};
-    if constexpr (kBandMix) {
-      // the numerator band steps (log space: two transcendentals each, every
-      // d of the group computed and kept only while d <= fl + 1) between the
-      // MFMAs of the core product: the wave issues them while its own
-      // dependent MFMA chain runs
-      float2 gv[PPL][kGrp + 1];
-      if (bands) {
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        __builtin_amdgcn_wave_barrier();
 #pragma unroll
-        for (int r = 0; r < PPL; ++r)
-#pragma unroll
-          for (int d = 0; d <= kGrp; ++d) gv[r][d] = sg[lane + 64 * r + d];
-      }
-#pragma unroll
-      for (int s = 0; s < 16; ++s) {
-        D = __builtin_amdgcn_mfma_f32_32x32x2f32(A[s], X[s], D, 0, 0, 0);
-        const int r = s / kGrp, d = kGrp - s % kGrp;
-        if (bands && r < PPL) {
-          const float nv = lse2_b2(nbd[r][d] + gv[r][d].x, nbd[r][d - 1] + gv[r][d].y);
-          nbd[r][d] = d <= flg + 1 ? nv : nbd[r][d];
-        }
-      }
-      if (bands) {
-#pragma unroll
-        for (int r = 0; r < PPL; ++r) nbd[r][0] += gv[r][0].x;
-        if (flg == kGrp - 1 || f == nt - 1) {  // source-major: 32 bytes per position
-          const int g0 = jg * (kGrp + 1) * NPG;
-#pragma unroll
-          for (int r = 0; r < PPL; ++r)
-            if (lane + 64 * r < NPG) {
-              const int u = lane + 64 * r;
-              st_wt4(nbr, g0 + 8 * u, nbd[r][0], nbd[r][1], nbd[r][2], nbd[r][3]);
-              st_wt4(nbr, g0 + 8 * u + 4, nbd[r][4], nbd[r][5], nbd[r][6], nbd[r][7]);
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-      }
-    } else {
-#pragma unroll
-      for (int s = 0; s < 16; ++s) D = __builtin_amdgcn_mfma_f32_32x32x2f32(A[s], X[s], D, 0, 0, 0);
-    }
+    for (int s = 0; s < 16; ++s) D = __builtin_amdgcn_mfma_f32_32x32x2f32(A[s], X[s], D, 0, 0, 0);
     // + Dg X: row kstep(r, h) of X times that state's blank self loop
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -870,7 +631,7 @@ LT_DEVINL void transfer_role(const CkArgs& a, int b, int k, int wave) {
     float cm = fmaxf(max3_raw(D[0], D[1], D[2]), max3_raw(D[3], D[4], D[5]));
 #pragma unroll
     for (int r = 6; r < 16; r += 2) cm = max3_raw(cm, D[r], D[r + 1]);
-    cm = kDppRed ? half_max(cm) : fmaxf(cm, half_other(cm));
+    cm = half_max(cm);
     int e;
     frexpf(cm, &e);
     e = cm > 0.f ? e : 0;
@@ -878,34 +639,16 @@ LT_DEVINL void transfer_role(const CkArgs& a, int b, int k, int wave) {
     for (int r = 0; r < 16; ++r) X[r] = ldexpf(D[r], -e);
     ej += e;
   };
-  if constexpr (kALds) {
-    // LT_CK_ALDS: the chunk's frames through a two-slot LDS ring per wave
-    // (LDS-DMA, 16 bytes a lane, a_ni wave instructions a frame) and into F
-    // one step ahead: frame f + 2's DMA is issued at the start of step f, so
-    // every frame has more than a step to land (the register prefetch gave
-    // it two thirds of one), with no registers held for it
-    aissue(0);
-    if (nt > 1) aissue(1);
-    wait_vmcnt(nt > 1 ? a.a_ni : 0);
-    lds_frame<BF16, PPL, FULL>(aframe(0), fo, fr);
-    for (int f = 0; f < nt; ++f) step(fr, f, f + 1 < nt);
-    if (lane < nt) a.cf[(long long)b * a.T + t0 + lane] = cfl_lane;
-  } else if constexpr (kApf == 1) {
-    // one frame in registers ahead
-    load_frame<BF16, PPL, FULL>(frame_ptr(0), frame_bytes(0), fo, fr);
-    for (int f = 0; f < nt; ++f) step(fr, f, f + 1 < nt);
-  } else {
-    // two frames in registers ahead, the buffers alternating (the reloads
-    // are unconditional, clamped to the chunk's last frame, so the
-    // compiler's vmcnt count across the two buffers stays exact)
-    FrameRegs<BF16, PPL> fr2;
-    load_frame<BF16, PPL, FULL>(frame_ptr(0), frame_bytes(0), fo, fr);
-    load_frame<BF16, PPL, FULL>(frame_ptr(1), frame_bytes(1), fo, fr2);
-    for (int f = 0; f < nt; f += 2) {
-      step(fr, f, true);
-      if (f + 1 < nt) step(fr2, f + 1, true);
-    }
-  }
+  // the chunk's frames through the wave's two-slot LDS ring (LDS-DMA, 16
+  // bytes a lane, a_ni wave instructions a frame) and into F one step ahead:
+  // frame f + 2's DMA is issued at the start of step f, so every frame has
+  // more than a step to land, with no registers held for it
+  aissue(0);
+  if (nt > 1) aissue(1);
+  wait_vmcnt(nt > 1 ? a.a_ni : 0);
+  lds_frame<BF16, PPL, FULL>(aframe(0), fo, fr);
+  for (int f = 0; f < nt; ++f) step(fr, f, f + 1 < nt);
+  if (lane < nt) a.cf[(long long)b * a.T + t0 + lane] = cfl_lane;
   CK_ASTAMP(2);
 
   const __amdgpu_buffer_rsrc_t rr = wt_rsrc(a.rec + (long long)id * kRec, 4 * kRec);
@@ -937,17 +680,19 @@ LT_DEVINL void transfer_role(const CkArgs& a, int b, int k, int wave) {
 
 // Phase B's side of the hand-off, one wave: chunks [0, hi] (forward walks)
 // or [lo, Kl) (backward walks) are known published. ensure() polls 64 flags
-// per pass with relaxed agent-scope loads (s_sleep between passes), and one
-// agent-scope acquire follows every pass that extends the range, so the
-// wave's own plain loads of the newly published records see them (no other
-// wave reads through this acquire). A flag of 2 marks a chunk outside the
-// fast path's range (bad). A bounded spin: on timeout (a placement that never
-// schedules the producer) ok = 0, the range is taken as covered, and the
-// utterance goes to the frame-serial kernels.
-// A flag poll and the agent-scope acquire as inline asm, each ending in
-// its own vmcnt(0): the compiler sees no memory instruction of its own in a
-// walk's step loop, so it has no reason to drain the walk's in-flight
-// LDS-DMA record loads at every step (it did for the builtin forms).
+// per pass with sc1 loads (s_sleep between passes). What the flags publish
+// (phase A's records and bands, and likewise the boundary rows the phase-2
+// walks publish for phase C) was stored write-through and is read with sc1
+// loads, which bypass the reading CU's L1: no acquire, no L1 invalidation
+// per poll (buffer_inv sc1 cost ~1.7 us a poll, more with four workgroups
+// on the CU). A flag of 2 marks a chunk outside the fast path's range (bad).
+// A bounded spin: on timeout (a placement that never schedules the producer)
+// ok = 0, the range is taken as covered, and the utterance goes to the
+// frame-serial kernels.
+// A flag poll as inline asm ending in its own vmcnt(0): the compiler sees no
+// memory instruction of its own in a walk's step loop, so it has no reason to
+// drain the walk's in-flight LDS-DMA record loads at every step (it did for
+// the builtin form).
 LT_DEVINL unsigned long long poll_flag(const unsigned long long* p) {
   unsigned long long v;
   asm volatile("global_load_dwordx2 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
@@ -961,8 +706,8 @@ LT_DEVINL unsigned flag_state(unsigned long long v, unsigned long long tag) {
 LT_DEVINL int prog_count(unsigned long long v, unsigned long long tag) {
   return (v & ~0xFFFFFFull) == tag ? (int)(v & 0xFFFFFF) : 0;
 }
-// L1-bypassing loads of another workgroup's data published in this launch
-// (LT_CK_NOACQ): 16 bytes, one float
+// L1-bypassing loads of another workgroup's data published in this launch:
+// 16 bytes, one float
 // (a buffer load: the compiler counts it in vmcnt, unlike an asm load)
 LT_DEVINL float4 ld_sc1x4(__amdgpu_buffer_rsrc_t r, int byte_off) {
   const v4u v = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0x10);
@@ -971,9 +716,6 @@ LT_DEVINL float4 ld_sc1x4(__amdgpu_buffer_rsrc_t r, int byte_off) {
 }
 LT_DEVINL float ld_sc1(const float* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-LT_DEVINL void acquire_agent() {
-  asm volatile("s_waitcnt vmcnt(0)\n\tbuffer_inv sc1\n\ts_waitcnt vmcnt(0)" ::: "memory");
 }
 struct ChunkReady {
   const unsigned long long* f;
@@ -1001,7 +743,6 @@ struct ChunkReady {
       take(v, lane, &c);
       if (c) {
         hi += c;
-        if (!kNoAcq) acquire_agent();
       } else if (spins > kSpinMax) {
         timeout();
       } else {
@@ -1018,7 +759,6 @@ struct ChunkReady {
       take(v, lane, &c);
       if (c) {
         lo -= c;
-        if (!kNoAcq) acquire_agent();
       } else if (spins > kSpinMax) {
         timeout();
       } else {
@@ -1029,8 +769,9 @@ struct ChunkReady {
 };
 
 // ---------------------------------------------------------------------------
-// B: chunk boundaries (one workgroup per utterance, 4 waves). Records and
-// numerator rows are prefetched into registers (the compiler's own waits).
+// B: chunk boundaries (one workgroup per utterance, 4 waves). The den walks'
+// records stream through an LDS ring; the numerator's band rows are
+// prefetched into registers (the compiler's own waits).
 // ---------------------------------------------------------------------------
 struct RecAlpha {  // what lane i (< 32) needs of one record for the alpha step
   float4 x[8];     // X[i][0..31]
@@ -1186,15 +927,10 @@ LT_DEVINL void num_walk(const CkArgs& a, int b, int lane, int nf, int Kl, int nl
 #pragma unroll
     for (int r = 0; r < PPL; ++r) {
       const int uc = min(lane + 64 * r, NPG - 1);
-      if constexpr (kNoAcq) {
-        const __amdgpu_buffer_rsrc_t rr =
-            __builtin_amdgcn_make_buffer_rsrc((void*)row, (short)0, 32 * NPG, 0x00020000);
-        g[r][0] = ld_sc1x4(rr, 32 * uc);
-        g[r][1] = ld_sc1x4(rr, 32 * uc + 16);
-      } else {
-        g[r][0] = row[2 * uc];
-        g[r][1] = row[2 * uc + 1];
-      }
+      const __amdgpu_buffer_rsrc_t rr =
+          __builtin_amdgcn_make_buffer_rsrc((void*)row, (short)0, 32 * NPG, 0x00020000);
+      g[r][0] = ld_sc1x4(rr, 32 * uc);
+      g[r][1] = ld_sc1x4(rr, 32 * uc + 16);
     }
   };
   auto step = [&](float4 (*g)[2], int q, int qn) {
@@ -1327,7 +1063,7 @@ LT_DEVINL void combine_role(const CkArgs& a, int b, int wave, unsigned char* dyn
   auto issue_rec = [&](int k, int n) {  // step n's record k (clamped to [0, Kl)) -> slot n mod kWalkSlots
     const int kc = min(max(k, 0), Kl - 1);
     dma_issue((const unsigned char*)a.rec, ((long long)b * a.K + kc) * (kRec * 4), kRec * 4,
-              ring_a + (unsigned)((n % kWalkSlots) * kWalkSlot), kRecNi, lane, 0, 1, kNoAcq);
+              ring_a + (unsigned)((n % kWalkSlots) * kWalkSlot), kRecNi, lane, 0, 1, true);
   };
   // step n's record has landed: the ring's issues and each step's one
   // boundary-row store, in issue order (vmcnt counts both, in order; the
@@ -1543,7 +1279,7 @@ __global__ __launch_bounds__(256, kAbWaves) void ck_ab_kernel(const CkArgs a) {
   int x = blockIdx.x;
   if (x >= a.wpos && x < a.wpos + nc) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ck_dyn[];
-    if (LT_CK_WPRIO) __builtin_amdgcn_s_setprio(LT_CK_WPRIO);  // the walks' chains first
+    __builtin_amdgcn_s_setprio(kWalkPrio);  // the walks' chains first
     combine_role<PPL, kWalkD<PPL>>(a, x - a.wpos, wave, ck_dyn, a.half ? kWalkFirst : kWalkFull);
     return;
   }
@@ -1594,11 +1330,11 @@ LT_DEVINL void store_dw(void* dW, long long e, float v) {
 // state's alpha and beta, W[0][0]
 constexpr int kFs = 8, kFsMa = 0, kFsA0 = 1, kFsMb = 2, kFsB0 = 3, kFsW00 = 4;
 // phase C's per-frame progress bits: den alpha / beta have passed the frame
-// (rows written, E_f read), numerator alpha / beta rows written; kFlNT
-// (LT_CK_NTERM): the frame's numerator terms stand in place of those rows
+// (rows written, E_f read), numerator alpha / beta rows written; kFlNT:
+// the frame's numerator terms stand in place of those rows
 constexpr int kFlA = 1, kFlB = 2, kFlNA = 4, kFlNB = 8, kFlAll = 15, kFlNT = 16;
 
-// LC (LT_CK_GEOM): the chunk length as a compile-time constant, for V = 32
+// LC: the chunk length as a compile-time constant, for V = 32
 // (FULL) and fp32 only, where the LDS budget admits L = 5 .. 8: the frame size, the
 // staging's DMA count and the carve's first regions (which depend on L, FB
 // and CP alone) are then immediates. LC = 0: every one of them from the
@@ -1619,7 +1355,7 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
   const int cOffAd = LC ? kAdC : a.c_off_ad, cOffBd = LC ? kBdC : a.c_off_bd;
   if (a.cont && (int)blockIdx.x < a.B) {  // phase 2 of utterance blockIdx.x's walks
     CK_STAMP(0);
-    if (LT_CK_WPRIO) __builtin_amdgcn_s_setprio(LT_CK_WPRIO);
+    __builtin_amdgcn_s_setprio(kWalkPrio);
     combine_role<PPL, kWalkDc<PPL>>(a, blockIdx.x, wave, lds, kWalkRest);
     CK_STAMP(4);
     return;
@@ -1660,28 +1396,13 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
   }
   const int nt = t1 - t0;
   CK_STAMP(0);
-  // the recursion roles rotate over the waves by workgroup (LT_CK_ROT), so
-  // the two den chains of the workgroups sharing a CU need not sit on the
-  // same two SIMDs
-  const int role = LT_CK_ROT == 1 ? (wave + (int)(blockIdx.x >> 3)) & 3
-                 : LT_CK_ROT == 2 ? (wave + (int)blockIdx.x) & 3 : wave;
-  // split staging (LT_CK_SPLIT): each den chain stages the half of W it
-  // reads first (alpha frames [0, hs), beta [hs, nt)) and starts on it while
-  // the other waves gather the tables; the chains take the numerator's arc
-  // weights out of their own frames before forming E there, and the
-  // numerator waves follow the chains' frame bits. One barrier (tables,
-  // offsets, flags), not two, and no wave waits for the whole chunk's DMA.
-  const bool split = LT_CK_SPLIT && !a.local && !LT_ABL(a, 4 | 8);
-  const int hs = (nt + 1) / 2;
-  // stage the chunk's live frames
+  // the recursion roles rotate over the waves by workgroup, so the two den
+  // chains of the workgroups sharing a CU need not sit on the same two SIMDs
+  const int role = (wave + (int)(blockIdx.x >> 3)) & 3;
+  const int hs = (nt + 1) / 2;  // den alpha forms E of frames [0, hs), den beta of [hs, nt)
+  // stage the chunk's live frames (all four waves)
   const long long off = e0 * (BF16 ? 2 : 4);
-  if (!split) {
-    dma_issue(a.W, off, (long long)nt * cFB, lds_base_addr(lds), cNi, lane, wave, kMargWaves);
-  } else if (role < 2) {
-    const int n1 = (int)(((off & 15) + (long long)hs * cFB + 1023) >> 10);
-    dma_range(a.W, off, (long long)nt * cFB, lds_base_addr(lds), role == 0 ? 0 : max(n1 - 1, 0),
-              role == 0 ? n1 : cNi, lane);
-  }
+  dma_issue(a.W, off, (long long)nt * cFB, lds_base_addr(lds), cNi, lane, wave, kMargWaves);
   unsigned char* wch = lds + (off & 15);
   float* xa = (float*)(lds + cOffAd);  // [L][CP] alpha_f, linear, max 1 (scale fs Ma)
   float* xb = (float*)(lds + cOffBd);  // [L][CP] beta_{f+1} of the core, linear, max 1
@@ -1712,27 +1433,11 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
       *cert_fail = 0;
     }
   };
-  // the split staging's tables, offsets and flags: the numerator waves
-  // (t2 = their thread in [0, 128)), the labels read by each of the two
-  if (split && role >= 2) {
-    const int t2 = (role - 2) * 64 + lane;
-    if (t2 < nt) cfl[t2] = a.cf[(long long)b * a.T + t0 + t2];
-    for (int j = lane; j < a.U; j += 64) labs[j] = a.labels[(long long)b * a.U + j];
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    for (int u = t2; u < NPG; u += 128) {
-      int bo, lo;
-      string_offsets(a, labs, u, &bo, &lo);
-      boff[u] = bo < 0 ? 0 : bo;
-      loff[u] = lo;
-    }
-    init_flags(t2);
-  }
-  if (!split && tid < nt) cfl[tid] = a.cf[(long long)b * a.T + t0 + tid];
+  if (tid < nt) cfl[tid] = a.cf[(long long)b * a.T + t0 + tid];
   // phase 2's boundaries this chunk needs (alpha at k, beta at k + 1): one
-  // lane polls the walks' progress words, then the agent-scope acquire
-  // before any wave's loads of them (after the barriers below); split: a
-  // numerator wave's lane, whose loads do not queue behind the W DMA
-  if (a.cont && (split ? (role == 2 && lane == 0) : tid == 0)) {
+  // lane polls the walks' progress words before any wave's (sc1) loads of
+  // them, after the barriers below
+  if (a.cont && tid == 0) {
     const int need_a = k - Kh, need_b = Kh - (k + 1);
     const unsigned long long* pg = a.prog + 4LL * b;
     int ok = 1;
@@ -1751,19 +1456,12 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
       }
       __builtin_amdgcn_s_sleep(2);
     }
-    if (!kNoAcq) acquire_agent();
     CK_STAMP(6);
     fl[2 * cL + 2] = ok;
   }
-  if (!split) {
-    gather_tables(a, b, labs, boff, loff, tid, blockDim.x);
-    wait_vmcnt(0);
-    __syncthreads();
-  } else {  // LDS only: the den chains' W DMA stays in flight
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  }
+  gather_tables(a, b, labs, boff, loff, tid, blockDim.x);
+  wait_vmcnt(0);
+  __syncthreads();
   if (a.cont && !fl[2 * cL + 2]) {
     if (tid == 0) a.uflag[b] = 1;
     return;
@@ -1786,10 +1484,10 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
   };
   // the numerator's arc weights leave W first (exact, log2); every read of
   // this pass issues before the barrier, every E store after it
-  if (!split && kGShift) {
-    // LT_CK_GSHIFT: thread = (frame of the pass, position), PW positions x
-    // FPP frames a pass (128 x 2 for PPL 2, 64 x 4 for PPL 1): the position's
-    // offsets and masks once per thread, the frame by a shift; NU passes
+  {
+    // thread = (frame of the pass, position), PW positions x FPP frames a
+    // pass (128 x 2 for PPL 2, 64 x 4 for PPL 1): the position's offsets and
+    // masks once per thread, the frame by a shift, no division; NU passes
     // held in registers (a chunk of up to NU * FPP frames: no dead pass at
     // the lengths the LDS budget gives long strings), the rest one by one
     constexpr int PW = 64 * PPL, FPP = 64 * kMargWaves / PW, NU = PPL == 1 ? 2 : 3;
@@ -1815,47 +1513,10 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
       const int f = FPP * i + f0;
       if (f < nt && u < NPG) nw[f * NPG + u] = g2[i];
     }
-  } else if (!split) {
-    float2 g2[4];
-    const int nnw = nt * NPG;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int x = min(tid + 64 * kMargWaves * i, nnw - 1);
-      const int f = x / NPG, u = x - f * NPG;
-      const unsigned char* fr = wch + f * cFB;
-      const int lo = loff[u];
-      const float wb = ldsw<BF16>(fr, boff[u]), wl = ldsw<BF16>(fr, max(lo, 0));
-      g2[i] = make_float2(u < NP ? wb * kLog2e : -kInf, (u >= 1 && u < NP) ? wl * kLog2e : -kInf);
-    }
-    for (int x = tid + 4 * 64 * kMargWaves; x < nnw; x += 64 * kMargWaves) {  // long strings
-      const int f = x / NPG, u = x - f * NPG;
-      const unsigned char* fr = wch + f * cFB;
-      const int lo = loff[u];
-      const float wb = ldsw<BF16>(fr, boff[u]), wl = ldsw<BF16>(fr, max(lo, 0));
-      nw[x] = make_float2(u < NP ? wb * kLog2e : -kInf, (u >= 1 && u < NP) ? wl * kLog2e : -kInf);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (tid + 64 * kMargWaves * i < nnw) nw[tid + 64 * kMargWaves * i] = g2[i];
   }
-  if (!split) {
-    if (tid < nt) fs[tid * kFs + kFsW00] = ldsw<BF16>(wch + tid * cFB, 0) * kLog2e;
-    init_flags(tid);
-    __syncthreads();  // nw, fs, fl and the job order for every wave
-  }
-  // split: frame f's numerator arc weights and W00, taken by the den chain
-  // that owns f out of its W before E overwrites it (one wave, LDS in order)
-  auto own_arcs = [&](int f, const unsigned char* fr) -> float {
-    for (int u = lane; u < NPG; u += 64) {
-      const int lo = loff[u];
-      const float wb = ldsw<BF16>(fr, boff[u]), wl = ldsw<BF16>(fr, max(lo, 0));
-      nw[f * NPG + u] =
-          make_float2(u < NP ? wb * kLog2e : -kInf, (u >= 1 && u < NP) ? wl * kLog2e : -kInf);
-    }
-    const float w = ldsw<BF16>(fr, 0) * kLog2e;
-    if (lane == 0) fs[f * kFs + kFsW00] = w;
-    return w;
-  };
+  if (tid < nt) fs[tid * kFs + kFsW00] = ldsw<BF16>(wch + tid * cFB, 0) * kLog2e;
+  init_flags(tid);
+  __syncthreads();  // nw, fs, fl and the job order for every wave
   CK_STAMP(5);
   // every LDS load below is unconditional (clamped index, unused values
   // masked afterwards): a load under a branch would pay its full latency
@@ -1879,8 +1540,8 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
   };
 
-  // LT_CK_PRIO: the den chains issue ahead of the other waves on their SIMD
-  if (LT_CK_PRIO && role < 2) __builtin_amdgcn_s_setprio(LT_CK_PRIO);
+  // the den chains issue ahead of the other waves on their SIMD
+  if (role < 2) __builtin_amdgcn_s_setprio(kDenPrio);
   if (role == 0 && !a.local && !LT_ABL(a, 4)) {
     // ---- den alpha in scaled linear space. Lane p in [1, V]: alpha_f[p] =
     // al 2^S (log2 units relative to the walk's offset); each frame the
@@ -1898,12 +1559,11 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
     const int qe = min(q, V - 1) + 1;
     const bool core = lane >= 1 && lane <= V;
     const float* xp = a.abd + ((long long)b * (a.K + 1) + k) * CP + min(lane, C - 1);
-    const float xr = kNoAcq ? ld_sc1(xp) : *xp;
+    const float xr = ld_sc1(xp);
     const float x0 = lane < C ? xr : -kInf;
     float a0 = first_lane(x0);
     float S = wmax_u(core ? x0 : -kInf);  // -inf: no core state reached yet
     float al = (core && S != -kInf) ? __builtin_amdgcn_exp2f(x0 - S) : 0.f;
-    if (split) wait_vmcnt(0);  // this wave's half of W
     // frame f's E terms of the lane (its sources' arcs into qe, source 32,
     // qe's blank self loop) and W00: alpha's own frames [0, hs) from W, their
     // E stored to its home; beta's once beta has passed them
@@ -1913,7 +1573,6 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
       const float cl = cfl[f];
       w00 = fs[f * kFs + kFsW00];
       if (f < hs) {
-        if (split) w00 = own_arcs(f, fr);
 #pragma unroll
         for (int m = 0; m < 16; ++m) e[m] = ldsw<BF16>(fr, min(16 * h + m, C - 1) * R + qe);
         e32 = ldsw<BF16>(fr, min(32, C - 1) * R + qe);
@@ -1929,21 +1588,16 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
         if (lane == 0) ef[0] = 0.f;  // (0, 0) is taken in log2 (xb[0] = 0)
       } else {
         wait_bits(f, kFlB);
-        if (split) w00 = fs[f * kFs + kFsW00];
 #pragma unroll
         for (int m = 0; m < 16; ++m) e[m] = ef[min(16 * h + m, C - 1) * R + qe];
         e32 = ef[min(32, C - 1) * R + qe];
         eb = ef[qe * R];
       }
     };
-    // LT_CK_EPIPE: alpha's own frames' E a step ahead (only those: fetching
-    // one of beta's frames early would wait on beta while beta waits on this
-    // chain's previous frame)
     float e[16], e32 = 0.f, eb = 0.f, w00 = 0.f;
-    if (kEpipe && nt > 0) get_e(0, e, e32, eb, w00);  // hs >= 1: frame 0 is alpha's
     for (int f = 0; f < nt; ++f) {
       const float cl = cfl[f];
-      if (!kEpipe || f >= hs) get_e(f, e, e32, eb, w00);
+      get_e(f, e, e32, eb, w00);
       const float mc = wmax_u(core ? al : 0.f);
       int ex;
       (void)frexpf(mc, &ex);
@@ -1951,28 +1605,12 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
       // xa = alpha_f over 2^Ma (the marginals' row) and the step's operand
       // row buf (36 floats, 0 past V)
       const float xv = lane == 0 ? __builtin_amdgcn_exp2f(a0 - Ma) : al * __builtin_amdgcn_exp2f(S - Ma);
-      if constexpr (kPredSt) {
-        // two unconditional stores, no exec-mask cluster: lanes 36 / 37 of the
-        // first carry the (wave-uniform) Ma / a0 to fs, the lanes past it land
-        // in the row's unused slots [36, 64); the lanes past C of the second
-        // land there too
-        float* p0 = lane == 36 ? fs + f * kFs + kFsMa : lane == 37 ? fs + f * kFs + kFsA0 : buf + lane;
-        *p0 = lane == 36 ? Ma : lane == 37 ? a0 : xv;
-        float* p1 = lane < C ? xa + f * CP + lane : buf + 36 + (lane & 15);
-        *p1 = xv;
-      } else {
       if (lane < 36) buf[lane] = xv;
       if (lane < C) xa[f * CP + lane] = xv;
       if (lane == 0) {
         fs[f * kFs + kFsMa] = Ma;
         fs[f * kFs + kFsA0] = a0;
       }
-      }
-      // LT_CK_EPIPE: the next frame's E under this step's LDS round trip
-      // (a wave issues in order: fetched at the top of the next step, its
-      // loads and exponentials sat on the chain)
-      float en[16], en32 = 0.f, enb = 0.f, wn00 = 0.f;
-      if (kEpipe && f + 1 < hs) get_e(f + 1, en, en32, enb, wn00);
       __builtin_amdgcn_s_waitcnt(0xc07f);
       __builtin_amdgcn_wave_barrier();
       float s0 = 0.f, s1 = 0.f;
@@ -1993,13 +1631,6 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
       al = core ? sh : 0.f;
       __builtin_amdgcn_wave_barrier();
       mark(f, kFlA);
-      if (kEpipe && f + 1 < hs) {
-#pragma unroll
-        for (int m = 0; m < 16; ++m) e[m] = en[m];
-        e32 = en32;
-        eb = enb;
-        w00 = wn00;
-      }
     }
   } else if (role == 1 && !a.local && !LT_ABL(a, 4)) {
     // ---- den beta, the same scaled linear space; frame f gets beta_{f+1}.
@@ -2011,12 +1642,11 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
     const int pe = min(j, V - 1) + 1;
     const bool core = lane >= 1 && lane <= V;
     const float* xp = a.bbd + ((long long)b * (a.K + 1) + k + 1) * CP + min(lane, C - 1);
-    const float xr = kNoAcq ? ld_sc1(xp) : *xp;
+    const float xr = ld_sc1(xp);
     const float x0 = lane < C ? xr : -kInf;
     float b0 = first_lane(x0);
     float S = safe_max(wmax_u(core ? x0 : -kInf));
     float be = core ? __builtin_amdgcn_exp2f(x0 - S) : 0.f;
-    if (split) wait_vmcnt(0);  // this wave's half of W
     // frame f's E terms of the lane (source pe's arcs, its blank, E[0][j+1])
     // and W00: beta's own frames [hs, nt) from W, alpha's once alpha passed them
     auto get_e = [&](int f, float* e, float& eb, float& e0y, float& w00) {
@@ -2025,7 +1655,6 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
       const float cl = cfl[f];
       w00 = fs[f * kFs + kFsW00];
       if (f >= hs) {
-        if (split) w00 = own_arcs(f, fr);
 #pragma unroll
         for (int m = 0; m < 16; ++m) e[m] = ldsw<BF16>(fr, pe * R + min(16 * h + m + 1, V));
         eb = ldsw<BF16>(fr, pe * R);
@@ -2041,43 +1670,28 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
         if (lane == 0) ef[0] = 0.f;
       } else {
         wait_bits(f, kFlA);
-        if (split) w00 = fs[f * kFs + kFsW00];
 #pragma unroll
         for (int m = 0; m < 16; ++m) e[m] = ef[pe * R + min(16 * h + m + 1, V)];
         eb = ef[pe * R];
         e0y = ef[min(j, V - 1) + 1];
       }
     };
-    // LT_CK_EPIPE: beta's own frames' E a step ahead (as alpha's)
     float e[16], eb = 0.f, e0y = 0.f, w00 = 0.f;  // e0y = E[0][j+1]
-    if (kEpipe && nt - 1 >= hs) get_e(nt - 1, e, eb, e0y, w00);
     for (int f = nt - 1; f >= 0; --f) {
       const float cl = cfl[f];
-      if (!kEpipe || f < hs) get_e(f, e, eb, e0y, w00);
+      get_e(f, e, eb, e0y, w00);
       const float mc = wmax_u(be);
       int ex;
       (void)frexpf(mc, &ex);
       const float Mb = mc > 0.f ? S + (float)ex : S;
       const float xv = be * __builtin_amdgcn_exp2f(S - Mb);  // <= 1
       // buf[y-1] = xb[y] for core y; 0 past V
-      if constexpr (kPredSt) {
-        // as alpha's: lanes 33 / 34 carry Mb / b0, lane 0 and the lanes past
-        // 34 land in the row's unused slots [32, 64)
-        float* p0 = lane == 33 ? fs + f * kFs + kFsMb : lane == 34 ? fs + f * kFs + kFsB0
-                  : (lane >= 1 && lane <= 32) ? buf + lane - 1 : buf + 32 + (lane & 31);
-        *p0 = lane == 33 ? Mb : lane == 34 ? b0 : xv;
-        float* p1 = lane < C ? xb + f * CP + lane : buf + 32 + (lane & 31);
-        *p1 = xv;
-      } else {
       if (lane >= 1 && lane <= 32) buf[lane - 1] = xv;
       if (lane < C) xb[f * CP + lane] = xv;
       if (lane == 0) {
         fs[f * kFs + kFsMb] = Mb;
         fs[f * kFs + kFsB0] = b0;
       }
-      }
-      float en[16], enb = 0.f, en0y = 0.f, wn00 = 0.f;
-      if (kEpipe && f - 1 >= hs) get_e(f - 1, en, enb, en0y, wn00);
       __builtin_amdgcn_s_waitcnt(0xc07f);
       __builtin_amdgcn_wave_barrier();
       float s0 = 0.f, s1 = 0.f;
@@ -2100,13 +1714,6 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
       be = core ? sh : 0.f;
       __builtin_amdgcn_wave_barrier();
       mark(f, kFlB);
-      if (kEpipe && f - 1 >= hs) {
-#pragma unroll
-        for (int m = 0; m < 16; ++m) e[m] = en[m];
-        eb = enb;
-        e0y = en0y;
-        w00 = wn00;
-      }
     }
   } else if (role == 2 && !LT_ABL(a, 8)) {
     // ---- num alpha (log2): al'[u] = al[u] + blank(u) (+) al[u-1] + arc(u)
@@ -2115,11 +1722,10 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
 #pragma unroll
     for (int r = 0; r < PPL; ++r) {
       const int u = lane + 64 * r, uc = min(u, NPG - 1);
-      const float v = kNoAcq ? ld_sc1(src + uc) : src[uc];  // log2, relative to the walk's offset
+      const float v = ld_sc1(src + uc);  // log2, relative to the walk's offset
       al[r] = u < NPG ? v : -kInf;
     }
     for (int f = 0; f < nt; ++f) {
-      if (split) wait_bits(f, f < hs ? kFlA : kFlB);  // nw[f] from its den chain
       float prev = -kInf, nv[PPL];
 #pragma unroll
       for (int r = 0; r < PPL; ++r) {
@@ -2143,25 +1749,10 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
 #pragma unroll
     for (int r = 0; r < PPL; ++r) {
       const int u = lane + 64 * r, uc = min(u, NPG - 1);
-      const float v = kNoAcq ? ld_sc1(src + uc) : src[uc];
+      const float v = ld_sc1(src + uc);
       be[r] = u < NPG ? v : -kInf;
     }
-    if (a.pf) {  // the chunk of the block about a.pf dispatches later, into L2
-      const int c2 = c + a.pf;
-      if (c2 < a.B * a.K) {
-        const int j2 = c2 / a.B, b2 = c2 - j2 * a.B;
-        int nf2 = a.nfr[b2];
-        nf2 = nf2 < 0 ? 0 : (nf2 > a.T ? a.T : nf2);
-        const int Kl2 = (nf2 + cL - 1) / cL, Kh2 = Kl2 / 2;
-        const int k2 = j2 < 2 * Kh2 ? ((j2 & 1) ? Kh2 - 1 - (j2 >> 1) : Kh2 + (j2 >> 1)) : j2;
-        const int t02 = k2 * cL, t12 = max(t02, min(t02 + cL, nf2));
-        if (t12 > t02)
-          pf_lines(a.W, ((long long)b2 * a.T + t02) * FR * (BF16 ? 2 : 4),
-                   (long long)(t12 - t02) * cFB, lds_base_addr((unsigned char*)buf), lane);
-      }
-    }
     for (int f = nt - 1; f >= 0; --f) {
-      if (split) wait_bits(f, f < hs ? kFlA : kFlB);
       float nx[PPL], nv[PPL];
 #pragma unroll
       for (int r = 0; r < PPL; ++r) nx[r] = rot_next(be[r]);
@@ -2182,7 +1773,7 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
   } else {  // a recursion this chunk does not run (local / ablations): nothing to wait for
     mark_all(role == 0 ? kFlA : role == 1 ? kFlB : role == 2 ? kFlNA : kFlNB);
   }
-  if (LT_CK_PRIO && role < 2) __builtin_amdgcn_s_setprio(0);
+  if (role < 2) __builtin_amdgcn_s_setprio(0);
   CK_STAMP(2);
 
   // ---- the numerator's marginal terms of frame f (log2 -> linear over the
@@ -2211,14 +1802,17 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
     zn = wsum_u(zn);
     return zn > 0.f ? g / zn : 0.f;
   };
-  // LT_CK_NTERM: the numerator chains end long before the den chains, so
-  // their waves form the terms of the last jobs' frames now (from job jpre
-  // on, even / odd rank in the marginals' order), behind the two numerator
-  // bits alone, and leave what the marginal job adds to dW, -sb gn and
-  // -sl gn, in the frame's an / bn rows (dead otherwise: the wave holds its
-  // whole row, the u - 1 neighbour included, before it overwrites)
-  const int jpre = kNTerm == 1 ? 0 : max(nt - 2, 0);  // the first job with its terms ready
-  if (kNTerm && role >= 2) {
+  // The numerator chains end long before the den chains, so their waves form
+  // the terms of the last two jobs' frames now (from job jpre on, one each:
+  // the jobs the den chains' waves take when they end), behind the two
+  // numerator bits alone, and leave what the marginal job adds to dW, -sb gn
+  // and -sl gn, in the frame's an / bn rows (dead otherwise: the wave holds
+  // its whole row, the u - 1 neighbour included, before it overwrites).
+  // Every other frame's terms are formed inside its marginal job (for every
+  // frame here it measured slower: it piles the numerator work of all frames
+  // on two waves that are issue-bound beside the prioritised den chains).
+  const int jpre = max(nt - 2, 0);  // the first job with its terms ready
+  if (role >= 2) {
     for (int jb = jpre + role - 2; jb < nt; jb += 2) {
       const int f = ford[jb];
       wait_bits(f, kFlNA | kFlNB);
@@ -2241,21 +1835,17 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
 
   // ---- marginals, one wave per frame: den - num, each normalised by its
   // frame total (alignments.py:311-317; numerator: reverse of :320-329).
-  // Den in rows: lane (y, h) = column y = lane & 31 of rows p = 2 m + h,
-  // then column 32 (lane p); arc (p, y) goes into q = y ? y : p. Den (p, y)
-  // = E[p][y] xa[p] xb[q] 2^(Ma + Mb + c - Z) except (0, 0), the only arc
-  // into the start state, taken in log2 (its beta may sit far above the
-  // core's; xb[0] = 0 keeps it out of the sum). Every other den term is
-  // <= 1 and the largest >= e^-61.
-  // That row-pair layout is LT_CK_DENCOL = 0. The default,
-  // LT_CK_DENCOL: lane (y', h) = column y = y' + 1 of rows p = 16 h + m (+
+  // Den by columns: lane (y', h) = column y = y' + 1 of rows p = 16 h + m (+
   // row 32 in h = 1), so the column's beta is one value per lane, and the
   // blank column's arc (p, 0) by lane p < C; xa[16 h ..] by 16-byte loads
-  // where the row is 36 floats (V = 32). The product order per element is
-  // the same, (E xa) xb; only the order of the frame total's sum differs.
-  constexpr int NROW = 17;  // row pairs: p = 2 m + h <= 33
+  // where the row is 36 floats (V = 32), by dwords otherwise. Arc (p, y)
+  // goes into q = y ? y : p. Den (p, y) = E[p][y] xa[p] xb[q]
+  // 2^(Ma + Mb + c - Z), the product taken as (E xa) xb, except (0, 0), the
+  // only arc into the start state, taken in log2 (its beta may sit far above
+  // the core's; xb[0] = 0 keeps it out of the sum). Every other den term is
+  // <= 1 and the largest >= e^-61.
+  constexpr int NROW = 17;  // rows per lane: p = 16 h + m, m < 16, and row 32
   const int y = lane & 31, h = lane >> 5;
-  const bool ycol = y < R;  // FULL: every lane
   int bo[PPL], lo[PPL];
 #pragma unroll
   for (int r = 0; r < PPL; ++r) {
@@ -2272,7 +1862,7 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
     jb = __builtin_amdgcn_readfirstlane(jb);
     if (jb >= nt || LT_ABL(a, 16)) break;
     const int f = ford[jb];
-    const bool pre = kNTerm && jb >= jpre;
+    const bool pre = jb >= jpre;
     const int want = pre ? (kFlA | kFlB | kFlNT) : kFlAll;
     for (;;) {
       const int bits = __builtin_amdgcn_readfirstlane(
@@ -2283,7 +1873,7 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     float* fb = eptr(f);  // E_f, then the frame's dW in place
     // the numerator's additions to dW: ready in the frame's an / bn rows
-    // (LT_CK_NTERM), or formed here
+    // (the last two jobs), or formed here
     float sb[PPL], sl[PPL];
     if (pre) {
 #pragma unroll
@@ -2306,61 +1896,36 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
       float t[NROW], ra[NROW], tc, sum;
       bool colc;
       const int pc = min(lane, C - 1);
-      if constexpr (kDenCol != 0) {
-        const int yq = min(y + 1, R - 1);
-        const bool yl = y + 1 < R;
-        const float xby = xbf[yq];  // column y' + 1's beta
-        const float eb = fb[pc * R], xap = xaf[pc], xbp = xbf[pc];  // blank column: arc (p, 0) into p
+      const int yq = min(y + 1, R - 1);
+      const bool yl = y + 1 < R;
+      const float xby = xbf[yq];  // column y' + 1's beta
+      const float eb = fb[pc * R], xap = xaf[pc], xbp = xbf[pc];  // blank column: arc (p, 0) into p
 #pragma unroll
-        for (int m = 0; m < 16; ++m) t[m] = fb[min(16 * h + m, C - 1) * R + yq];
-        t[16] = fb[min(32, C - 1) * R + yq];
-        if constexpr (FULL && kDenCol == 2) {
+      for (int m = 0; m < 16; ++m) t[m] = fb[min(16 * h + m, C - 1) * R + yq];
+      t[16] = fb[min(32, C - 1) * R + yq];
+      if constexpr (FULL) {
 #pragma unroll
-          for (int g4 = 0; g4 < 4; ++g4) {
-            const float4 x4 = *(const float4*)(xaf + 16 * h + 4 * g4);
-            ra[4 * g4 + 0] = x4.x;
-            ra[4 * g4 + 1] = x4.y;
-            ra[4 * g4 + 2] = x4.z;
-            ra[4 * g4 + 3] = x4.w;
-          }
-        } else {
-#pragma unroll
-          for (int m = 0; m < 16; ++m) ra[m] = xaf[min(16 * h + m, C - 1)];
-        }
-        ra[16] = xaf[min(32, C - 1)];
-        colc = lane < C;
-        tc = colc ? eb * xap * xbp : 0.f;
-        sum = tc;
-#pragma unroll
-        for (int m = 0; m < NROW; ++m) {
-          const bool live = yl && (m < 16 ? 16 * h + m < C : (h == 1 && C > 32));
-          const float v = t[m] * ra[m] * xby;
-          t[m] = live ? v : 0.f;
-          sum += t[m];
+        for (int g4 = 0; g4 < 4; ++g4) {
+          const float4 x4 = *(const float4*)(xaf + 16 * h + 4 * g4);
+          ra[4 * g4 + 0] = x4.x;
+          ra[4 * g4 + 1] = x4.y;
+          ra[4 * g4 + 2] = x4.z;
+          ra[4 * g4 + 3] = x4.w;
         }
       } else {
-        const int yc = min(y, R - 1);
-        const float xby = xbf[yc];  // column y's beta (y >= 1)
-        // rows: E, xa[p] and xb[p] (the blank column's beta) for p = 2 m + h
-        float rb[NROW];
 #pragma unroll
-        for (int m = 0; m < NROW; ++m) t[m] = fb[min(2 * m + h, C - 1) * R + yc];
+        for (int m = 0; m < 16; ++m) ra[m] = xaf[min(16 * h + m, C - 1)];
+      }
+      ra[16] = xaf[min(32, C - 1)];
+      colc = lane < C;
+      tc = colc ? eb * xap * xbp : 0.f;
+      sum = tc;
 #pragma unroll
-        for (int m = 0; m < NROW; ++m) ra[m] = xaf[min(2 * m + h, C - 1)];
-#pragma unroll
-        for (int m = 0; m < NROW; ++m) rb[m] = xbf[min(2 * m + h, C - 1)];
-        // column 32 (C = 33 only): lane p < 33
-        tc = fb[pc * R + (R - 1)] * xaf[pc] * xbf[R - 1];
-        colc = R == 33 && lane < 33;
-        tc = colc ? tc : 0.f;
-        sum = tc;
-#pragma unroll
-        for (int m = 0; m < NROW; ++m) {
-          const bool live = ycol && 2 * m + h < C && (R < 33 || y < 32);
-          const float v = t[m] * ra[m] * (y ? xby : rb[m]);
-          t[m] = live ? v : 0.f;
-          sum += t[m];
-        }
+      for (int m = 0; m < NROW; ++m) {
+        const bool live = yl && (m < 16 ? 16 * h + m < C : (h == 1 && C > 32));
+        const float v = t[m] * ra[m] * xby;
+        t[m] = live ? v : 0.f;
+        sum += t[m];
       }
       sum = wsum_u(sum);
       const float* fsf = fs + f * kFs;
@@ -2380,22 +1945,12 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
       const float m00 = g * __builtin_amdgcn_exp2f(v00 - zl);
       __builtin_amdgcn_s_waitcnt(0xc07f);
       __builtin_amdgcn_wave_barrier();
-      if constexpr (kDenCol != 0) {
 #pragma unroll
-        for (int m = 0; m < NROW; ++m) {
-          const int p = m < 16 ? 16 * h + m : 32;
-          if (y + 1 < R && (m < 16 ? p < C : (h == 1 && C > 32))) fb[p * R + y + 1] = t[m] * mult;
-        }
-        if (colc) fb[pc * R] = lane == 0 ? m00 : tc * mult;
-      } else {
-#pragma unroll
-        for (int m = 0; m < NROW; ++m) {
-          const int p = 2 * m + h;
-          if (ycol && p < C && (R < 33 || y < 32))
-            fb[p * R + y] = (m == 0 && lane == 0) ? m00 : t[m] * mult;
-        }
-        if (colc) fb[pc * R + (R - 1)] = tc * mult;
+      for (int m = 0; m < NROW; ++m) {
+        const int p = m < 16 ? 16 * h + m : 32;
+        if (y + 1 < R && (m < 16 ? p < C : (h == 1 && C > 32))) fb[p * R + y + 1] = t[m] * mult;
       }
+      if (colc) fb[pc * R] = lane == 0 ? m00 : tc * mult;
     } else {
       __builtin_amdgcn_s_waitcnt(0xc07f);
       __builtin_amdgcn_wave_barrier();
@@ -2483,7 +2038,6 @@ int ck_plan(const lt_problem* pb, int local_norm, CkArgs* a, CkLayout* w) {
   a->local = local_norm ? 1 : 0;
 #ifdef LT_DIAG
   a->dbg = ck_env("LT_CK_DBG", 0);
-  a->pf = ck_env("LT_CK_PF", LT_CK_PF);
   if (const char* sp = lt_impl::tune_str("LT_CK_STAMPS")) a->stamps = (long long*)strtoull(sp, nullptr, 0);
 #endif
   a->FB = (long long)a->FR * es;
@@ -2676,11 +2230,11 @@ int ck_launch_ab(CkArgs& a, bool bf16, hipStream_t st) {
   const int at = ck_env("LT_CHUNK_WALK_AT", std::max(0, 100 - 4800 / std::max(a.B, 1)));
   a.wpos = (int)(nwa * std::min(std::max(at, 0), 100) / 100);
   int rc = ck_launch(ck_kernel_ab(a.PPL, bf16, a.V == 32), (int)(a.nc + nwa),
-                     std::max(fuse ? kWalkLdsBytes : 0, kALds ? kALdsBytes : 0), st, a);
+                     std::max(fuse ? kWalkLdsBytes : 0, kALdsBytes), st, a);
   if (rc || fuse) return rc;
   return ck_launch(ck_kernel_b(a.PPL), a.B, kWalkLdsBytes, st, a);
 }
-// the V = 32 instantiation of chunk length L (LT_CK_GEOM), or nullptr
+// the V = 32 instantiation of chunk length LC
 // (fp32 only: for bf16 W the instantiations measured no gain, or a loss, and
 // spill more SGPRs than the run-time kernel, so bf16 keeps the run-time kernel)
 template <int LC>
@@ -2695,7 +2249,7 @@ int g_last_marg_len = 0;
 // the plan (tests compare the two bit for bit)
 const void* ck_kernel_c(int ppl, bool bf16, bool full, const CkArgs& a) {
   g_last_marg_len = 0;
-  if (kGeom && full && !bf16 && ck_env("LT_CHUNK_GENERIC", 0) == 0) {
+  if (full && !bf16 && ck_env("LT_CHUNK_GENERIC", 0) == 0) {
     // the instantiation must be the plan's: L, and the carve it implies
     const int fb = 33 * 33 * (bf16 ? 2 : 4);
     const int ni = ((a.L * fb + 30) / 16 + 63) / 64;

@@ -58,8 +58,8 @@ def report(s, head):
 
 report(s, '')
 print(f'span {s[:, 4].max() - s[:, 0].min()} cycles')
-# the marks are wave 0's, whose recursion rotates with the block (LT_CK_ROT
-# = 1: role (block >> 3) & 3): per role, `recursions` is that chain's own
+# the marks are wave 0's, whose recursion rotates with the block (role
+# (wave + (block >> 3)) & 3, so (block >> 3) & 3 for wave 0): per role, `recursions` is that chain's own
 # length and `marginals` what follows it up to the workgroup's last barrier
 for role, nm in enumerate(('den alpha', 'den beta', 'num alpha', 'num beta')):
   sel = ((blk >> 3) & 3) == role
