@@ -94,7 +94,8 @@ int lt_den_backward(const lt_problem* pb, const void* W,
 /* RecognitionLattice._string_forward (lattices.py:250-377): numerator
  * (intersection with the label string) shortest distance.
  *   labels [B,U] int32, num_labels [B] int32
- *   num [B] out; alpha_num [B,T,U+1] out (nullable). */
+ *   num [B] out; alpha_num [B,T,U+1] out (nullable): row t before frame t,
+ *   padding frames carry, as alpha. */
 int lt_num_forward(const lt_problem* pb, int32_t semiring, const void* W,
                    const int32_t* num_frames, const int32_t* labels,
                    const int32_t* num_labels, float* num, float* alpha_num,
@@ -103,7 +104,8 @@ int lt_num_forward(const lt_problem* pb, int32_t semiring, const void* W,
 /* RecognitionLattice.forward (lattices.py:131-183), fused denominator +
  * numerator in one launch (Log semiring).
  *   local_norm != 0: LocallyNormalizedWeightFn (lattices.py:178-179),
- *                    loss = -num and the denominator is skipped.
+ *                    loss = -num and the denominator is skipped: log_z = 0
+ *                    (here and in every loss entry point below).
  *   loss [B] out; log_z [B], num [B] out; alpha [B,T,C], alpha_num
  *   [B,T,U+1] out (needed by lt_loss_backward; nullable otherwise).
  *   Checkpointing mode (beta_num and arcs non-NULL, and beta unless
@@ -152,7 +154,9 @@ int lt_loss_backward(const lt_problem* pb, int32_t local_norm, const void* W,
  * out of its range or a hand-off wait timed out; no memset: the hand-off
  * words carry a per-call tag, so the workspace's contents do not matter;
  * under stream capture, where every replay would reuse the captured tag, a
- * memset node zeroes them instead). Other
+ * memset node zeroes them instead; an utterance whose string is unreachable
+ * or whose log_z is not finite is among those the frame-serial launch
+ * takes). Other
  * bigram shapes with 2B below the CU count run ONE fused launch (alpha and
  * beta recursions plus workgroups that turn every frame into marginals as
  * soon as both recursions have passed it; should a hand-off wait time out,

@@ -56,7 +56,8 @@ int lt_cpu_den_backward(const lt_problem* pb, const void* W, const int32_t* num_
 /* lt_loss_grad on the host: loss, log_z, num [B] (log_z / num nullable) and,
  * when dW is non-NULL, dW = grad[b] * d loss_b / dW (grad nullable = ones;
  * utterances with an unreachable string or a non-finite log_z get dW = 0;
- * padding frames 0). local_norm != 0: loss = -num (lattices.py:178-179). */
+ * padding frames 0). local_norm != 0: loss = -num (lattices.py:178-179) and
+ * log_z = 0. */
 int lt_cpu_loss_grad(const lt_problem* pb, int32_t local_norm, const void* W,
                      const int32_t* num_frames, const int32_t* labels,
                      const int32_t* num_labels, const float* grad, float* loss,

@@ -272,11 +272,9 @@ def loss_forward(W, num_frames, labels, num_labels, vocab_size, context_size, lo
   beta_num = _f32([B, T, U + 1], W) if checkpoints else None
   arcs = (torch.empty([B, 4 * (U + 1)], dtype=torch.int32, device=W.device)
           if checkpoints else None)
-  if local_norm:
-    log_z.zero_()
   _check(lib().lt_loss_forward(ctypes.byref(pb), int(bool(local_norm)), _ptr(W),
                                _ptr(num_frames), _ptr(labels), _ptr(num_labels), _ptr(loss),
-                               None if local_norm else _ptr(log_z), _ptr(num), _ptr(alpha),
+                               _ptr(log_z), _ptr(num), _ptr(alpha),
                                _ptr(an), _ptr(beta), _ptr(beta_num), _ptr(arcs), _stream()),
          'lt_loss_forward')
   if checkpoints:

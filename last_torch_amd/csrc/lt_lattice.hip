@@ -1113,6 +1113,11 @@ int lt_loss_forward(const lt_problem* pb, int32_t local_norm, const void* W,
   const bool bf16 = pb->weight_dtype == LT_DTYPE_BF16;
   const int flags = F_NUM | F_LOSS | (local_norm ? F_LOCAL : F_DEN);
   hipStream_t st = (hipStream_t)stream;
+  // no denominator runs under local_norm: log_z = 0, as every other route
+  // writes it (serial_loss, lt_chunk.hip, lt_table_loss_grad)
+  if (local_norm && log_z &&
+      (rc = hip_check(hipMemsetAsync(log_z, 0, sizeof(float) * pb->batch, st), "memset")))
+    return rc;
   // bigram with checkpoints: the pipelined two-factor alpha and beta
   // recursions in one launch (lt_pipe.hip). Without checkpoints the
   // frame-barrier kernel below is the faster one (measured: 0.45 vs 0.52 ms
@@ -1493,6 +1498,10 @@ int lt_loss_grad_ex(const lt_problem* pb, int32_t local_norm, int32_t design_in,
     // frames into dW while the frames are in the ring (lt_pipe.hip, mid mode)
     const size_t need = lt_impl::pipe_mid_workspace_bytes(pb);
     if (!workspace || workspace_bytes < need) return fail(LT_EINVAL, "workspace too small");
+    if (local_norm &&  // no denominator role runs: log_z = 0, as in lt_loss_forward
+        (rc = hip_check(hipMemsetAsync(log_z, 0, sizeof(float) * pb->batch, (hipStream_t)stream),
+                        "memset")))
+      return rc;
     if ((rc = lt_impl::launch_pipe(pb, local_norm, W, num_frames, labels, num_labels, loss, log_z,
                                    num, nullptr, nullptr, nullptr, nullptr, nullptr, 2, nullptr,
                                    stream, dW, 1, workspace)))
