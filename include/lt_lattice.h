@@ -491,5 +491,7 @@ const char* lt_version(void);
 #include "lt_sample.h"
 /* Posterior means of arc values and their gradients, likewise. */
 #include "lt_expect.h"
+/* Per-label emission posteriors of a label string, likewise. */
+#include "lt_posterior.h"
 
 #endif /* LT_LATTICE_H_ */

@@ -93,6 +93,8 @@ _SIG = {
     'lt_table_viterbi': [_G, _TP, _P, _P, _I32, _P, _P, _P, ctypes.c_size_t, _P],
     'lt_table_align_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_align': [_G, _TP] + [_P] * 8 + [ctypes.c_size_t, _P],
+    'lt_table_align_posteriors_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
+    'lt_table_align_posteriors': [_G, _TP] + [_P] * 7 + [ctypes.c_size_t, _P],
     'lt_table_sample_workspace_bytes': [_G, _TP, _I32, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_sample': [_G, _TP, _P, _P, _P, _P, _I32, ctypes.c_uint64, _P, _P, _P,
                         ctypes.c_size_t, _P],
@@ -123,12 +125,15 @@ _SIG = {
 }
 # the functions each header of the C ABI declares: include/lt_align.h (forced
 # alignment), include/lt_sample.h (path sampling), include/lt_expect.h
-# (posterior means of arc values) and include/lt_lattice.h (everything else)
+# (posterior means of arc values), include/lt_posterior.h (emission posteriors
+# of a label string) and include/lt_lattice.h (everything else)
 EXPORTED_ALIGN = ('lt_table_align_workspace_bytes', 'lt_table_align')
 EXPORTED_SAMPLE = ('lt_table_sample_workspace_bytes', 'lt_table_sample')
 EXPORTED_EXPECT = ('lt_table_expectation_workspace_bytes', 'lt_table_expectation')
+EXPORTED_POSTERIOR = ('lt_table_align_posteriors_workspace_bytes', 'lt_table_align_posteriors')
 EXPORTED = (tuple(n for n in _SIG
-                  if n not in EXPORTED_ALIGN + EXPORTED_SAMPLE + EXPORTED_EXPECT) +
+                  if n not in (EXPORTED_ALIGN + EXPORTED_SAMPLE + EXPORTED_EXPECT +
+                               EXPORTED_POSTERIOR)) +
             ('lt_last_error', 'lt_version'))
 
 
@@ -664,6 +669,41 @@ def table_align(graph, W, num_frames, labels, num_labels):
                               _ptr(labels), _ptr(num_labels), _ptr(out), _ptr(frames),
                               _ptr(weight), _ptr(ws), nbytes.value, _stream()), 'lt_table_align')
   return out, frames, weight
+
+
+def table_align_posteriors_supported(graph, W, labels):
+  """Whether lt_table_align_posteriors takes this problem (FrameDependent,
+  U <= 255): a host-only query, no launch. Other errors raise."""
+  pb = _tproblem(graph, W, labels.shape[-1])
+  nbytes = ctypes.c_size_t(0)
+  rc = lib().lt_table_align_posteriors_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
+                                                       ctypes.byref(nbytes))
+  if rc == LT_EUNSUPPORTED:
+    return False
+  _check(rc, 'lt_table_align_posteriors_workspace_bytes')
+  return True
+
+
+def table_align_posteriors(graph, W, num_frames, labels, num_labels):
+  """lt_table_align_posteriors: the emission posteriors of the label strings,
+  one launch. Returns (emission fp32 [B, T, U], log_prob fp32 [B]); raises
+  LatticeLibraryError (LT_EUNSUPPORTED) for FrameLabelDependent graphs or past
+  U = 255."""
+  pb = _tproblem(graph, W, labels.shape[-1])
+  B, T = W.shape[:2]
+  U = labels.shape[-1]
+  nbytes = ctypes.c_size_t(0)
+  _check(lib().lt_table_align_posteriors_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
+                                                         ctypes.byref(nbytes)),
+         'lt_table_align_posteriors_workspace_bytes')
+  ws = (torch.empty([nbytes.value], dtype=torch.uint8, device=W.device) if nbytes.value else None)
+  emission = _f32([B, T, U], W)
+  log_prob = _f32([B], W)
+  _check(lib().lt_table_align_posteriors(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W),
+                                         _ptr(num_frames), _ptr(labels), _ptr(num_labels),
+                                         _ptr(emission), _ptr(log_prob), _ptr(ws), nbytes.value,
+                                         _stream()), 'lt_table_align_posteriors')
+  return emission, log_prob
 
 
 def table_sample(graph, W, num_frames, log_z, alpha, num_samples, seed):

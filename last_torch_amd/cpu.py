@@ -3,8 +3,10 @@
 ``RecognitionLattice`` runs here when its arc weights live on the CPU and on
 the HIP kernels (liblt_lattice.so) when they live on a ROCm device: the
 device of the tensors picks the implementation, as in the reference, and
-there is no fallback from one to the other (a ROCm tensor never runs here;
-a missing HIP library raises).
+there is no fallback from one to the other (a ROCm tensor never runs on the
+host; a missing HIP library raises). The one function here that also takes
+ROCm tensors is align_posteriors, which then runs its torch ops on their
+device: RecognitionLattice.align_posteriors past its kernel's range.
 
 One formulation covers both alignment lattices and any context dependency.
 A frame of FrameDependent (K = 0) or FrameLabelDependent(K) is
@@ -30,6 +32,9 @@ MaxTropical's first-argmax rule prefers the blank, then fewer expansions.
   align         (not in the reference) forced alignment: the max-tropical
                                       string distance differentiated w.r.t.
                                       the string's lexical weights
+  align_posteriors (not in the reference) emission posteriors of the label
+                                      string: the Log string distance
+                                      differentiated w.r.t. the same weights
   sample        (not in the reference) paths from the posterior exp(w) / Z:
                                       Gumbel-max on Philox4x32-10, walked
                                       backwards over alpha (lt_sample.h)
@@ -131,9 +136,11 @@ def _string_distance(blank: torch.Tensor, lex: torch.Tensor, nf: torch.Tensor, n
   W = blank
   B, T = blank.shape[:2]
   U = lex.shape[-1]
-  zero = semiring.zeros([B, 1], W.dtype)
-  one = semiring.ones([], W.dtype)
-  alpha = torch.where(torch.arange(U + 1) == 0, one, semiring.zeros([], W.dtype)).expand(B, U + 1)
+  dev = W.device  # the host, or the weights' own device (align_posteriors past its kernel's range)
+  zero = semiring.zeros([B, 1], W.dtype, dev)
+  one = semiring.ones([], W.dtype, dev)
+  alpha = torch.where(torch.arange(U + 1, device=dev) == 0, one,
+                      semiring.zeros([], W.dtype, dev)).expand(B, U + 1)
   for t in range(T):
     lex_t = torch.cat([lex[:, t], zero], dim=-1)   # no arc out of position U
 
@@ -144,7 +151,7 @@ def _string_distance(blank: torch.Tensor, lex: torch.Tensor, nf: torch.Tensor, n
     alpha = torch.where(_live(nf, t), nxt, alpha)
   ok = (nl >= 0) & (nl <= U)
   num = torch.gather(alpha, 1, nl.clamp(0, U).long()[:, None])[:, 0]
-  return torch.where(ok, num, semiring.zeros([], W.dtype))
+  return torch.where(ok, num, semiring.zeros([], W.dtype, dev))
 
 
 def loss(W: torch.Tensor, nf: torch.Tensor, labels: torch.Tensor, nl: torch.Tensor,
@@ -227,6 +234,45 @@ def align(W: torch.Tensor, nf: torch.Tensor, labels: torch.Tensor, nl: torch.Ten
   b, t, u = torch.nonzero(taken, as_tuple=True)
   out[b, t, slot[b, t, u]] = true[b, u]
   return out.reshape(B, T * A), label_frames, dist
+
+
+def align_posteriors(W: torch.Tensor, nf: torch.Tensor, labels: torch.Tensor, nl: torch.Tensor,
+                     context: contexts.ContextDependency, alignment):
+  """Emission posteriors of the label string (include/lt_posterior.h): the
+  Log string distance differentiated with respect to the string's own
+  per-frame lexical weights (string_weights), align's construction in the Log
+  semiring. emission[b, t, u] = d log_prob / d lex_t[u] is the posterior
+  probability that the arc leaving string position u is taken on frame t
+  (FrameLabelDependent: summed over the frame's expansion slots). Returns
+  (emission [B, T, U], log_prob [B]), float32 (float64 for float64 weights). Rows t >= nf and
+  columns u >= nl are exactly 0; an utterance whose distance is not finite is
+  masked out of the differentiated sum: log_prob = -inf, emission all 0.
+  Labels outside 1..V are epsilons. Runs on W's device (the host for CPU
+  tensors; RecognitionLattice.align_posteriors runs it on a ROCm device past
+  the kernel's range, with the context as a NextStateTable on that device)."""
+  K = expansions(alignment)
+  B, T = W.shape[:2]
+  U = labels.shape[-1]
+  V = W.shape[-1] - 1
+  lab = labels.long()
+  lab = torch.where((lab >= 1) & (lab <= V), lab, torch.zeros_like(lab))
+  with torch.enable_grad():
+    Wd = W.detach()
+    if Wd.dtype != torch.float64:  # float64 stays (the tests' reference precision)
+      Wd = Wd.float()
+    blank, lex = string_weights(Wd, lab, context)
+    lex = lex.detach().requires_grad_(True)
+    dist = _string_distance(blank, lex, nf, nl, K, semirings.Log)
+    fin = torch.isfinite(dist.detach())
+    total = torch.where(fin, dist, torch.zeros_like(dist)).sum()
+    grad = (torch.autograd.grad(total, [lex], allow_unused=True)[0]
+            if total.requires_grad else None)
+  dist = dist.detach()
+  emission = torch.zeros([B, T, U], dtype=Wd.dtype, device=W.device)
+  if grad is not None:
+    emission = torch.where(fin[:, None, None], grad, emission)
+  log_prob = torch.where(fin, dist, torch.full_like(dist, -torch.inf))
+  return emission, log_prob
 
 
 def expectation(W: torch.Tensor, values: torch.Tensor, nf: torch.Tensor,

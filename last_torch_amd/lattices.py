@@ -18,6 +18,9 @@ weights once through the ``WeightFn`` plugin as a contiguous
   shortest_path   -> lt_viterbi
   align           -> lt_table_align (forced alignment; not in the reference);
                      past its range lt_table_num_backward (Max) compacted
+  align_posteriors -> lt_table_align_posteriors (emission posteriors of the
+                     label string; not in the reference); past its range the
+                     torch restatement (cpu.align_posteriors) on the device
   sample          -> lt_den_forward / lt_table_forward (Log) + lt_table_sample
                      (paths from the posterior; not in the reference)
   expectation     -> lt_table_expectation (posterior mean of arc values with
@@ -554,6 +557,70 @@ class RecognitionLattice(nn.Module, Generic[T]):
     return (self._home(alignment_labels.reshape(*batch_dims, -1), frames),
             self._home(label_frames.reshape(*batch_dims, -1), frames),
             self._home(weights.reshape(batch_dims), frames))
+
+  def align_posteriors(self, frames: torch.Tensor, num_frames: torch.Tensor,
+                       labels: torch.Tensor, num_labels: torch.Tensor, cache: Optional[T] = None):
+    """Soft forced alignment (not in the reference): with what probability is
+    each label of the transcript emitted on each frame, given the transcript
+    -- `align`'s question in the Log semiring. The definition is in
+    include/lt_posterior.h: with alpha / beta the Log forward / backward
+    vectors of the lattice intersected with the label string,
+
+        emission[t, u] = exp(alpha_t[u] + lex_t[u] + beta_{t+1}[u+1] - log_prob)
+                       = d log_prob / d lex_t[u],
+
+    the posterior probability that the arc leaving string position u (the
+    one that emits labels[u]) is taken on frame t; FrameLabelDependent sums
+    the frame's expansion slots. Labels outside 1..V are epsilons.
+
+    Returns (emission [batch..., T, U] float32, log_prob [batch...] float32),
+    frame-major like the arc weights, so
+    ``(arange(T)[:, None] * emission).sum(-2)`` is the expected emission frame
+    of each label. log_prob equals _string_forward(..., Log) up to rounding.
+    Two invariants hold for an aligned utterance (up to fp32 rounding):
+    ``emission.sum(-2)[..., u] == 1`` for u < num_labels (every label is
+    emitted exactly once), and on FrameDependent ``emission.sum(-1) <= 1``
+    per frame (a frame emits at most one label). emission is exactly 0 for
+    u >= num_labels and t >= num_frames. An utterance whose log_prob is not
+    finite (no path, -inf arcs on every path, num_labels outside [0, U]) has
+    log_prob = -inf and an all-zero emission, never NaN. No gradient flows
+    through either output.
+
+    ROCm tensors run one launch of lt_table_align_posteriors (FrameDependent,
+    U <= 255, fp32 or bf16 weights); FrameLabelDependent or longer strings
+    run the torch restatement (cpu.align_posteriors) on the tensors' own
+    device; CPU tensors run it on the host.
+    """
+    batch_dims = tuple(num_frames.shape)
+    if tuple(frames.shape[:-2]) != batch_dims:
+      raise ValueError('frames and num_frames have different batch_dims: '
+                       f'{tuple(frames.shape[:-2])} vs {batch_dims}')
+    if tuple(labels.shape[:-1]) != batch_dims:
+      raise ValueError('labels and num_frames have different batch_dims: '
+                       f'{tuple(labels.shape[:-1])} vs {batch_dims}')
+    if tuple(num_labels.shape) != batch_dims:
+      raise ValueError('num_labels and num_frames have different batch_dims: '
+                       f'{tuple(num_labels.shape)} vs {batch_dims}')
+    W, nf, batch_dims, B, _, _, _ = self._prepare(cache, frames, num_frames)
+    lab = torch.as_tensor(labels).reshape(B, -1).to(device=W.device, dtype=torch.int32).contiguous()
+    nl = _lengths(num_labels, B, W.device)
+    with torch.no_grad():
+      W = W.detach()
+      if W.device.type == 'cpu':
+        out = cpu.align_posteriors(W, nf, lab, nl.long(), self.context, self.alignment)
+      else:
+        graph = self._graph(W.device)
+        if _native.table_align_posteriors_supported(graph, W, lab):
+          out = _native.table_align_posteriors(graph, W, nf, lab, nl)
+        else:
+          # the same restatement on the device: the walk reads the graph's
+          # device copy of the next-state table, nothing visits the host
+          out = cpu.align_posteriors(W, nf.long(), lab, nl.long(),
+                                     contexts.NextStateTable(graph.table), self.alignment)
+    emission, log_prob = out
+    T_, U_ = W.shape[1], lab.shape[-1]
+    return (self._home(emission.float().reshape(*batch_dims, T_, U_), frames),
+            self._home(log_prob.float().reshape(batch_dims), frames))
 
   def sample(self, frames: torch.Tensor, num_frames: torch.Tensor, num_samples: int, seed: int,
              cache: Optional[T] = None):
