@@ -183,7 +183,8 @@ int lt_scale_grad(const lt_problem* pb, const float* grad, void* dW,
  * and T/L chunk steps (T/7 numerator group steps) instead of T.
  *   lt_chunk_forward  = RecognitionLattice.forward (lattices.py:131-183):
  *     loss [B] (log_z, num [B] nullable outputs); keeps the alpha / beta
- *     values at every chunk boundary in `state`.
+ *     values at every chunk boundary and the strings' gather tables in
+ *     `state`.
  *   lt_chunk_backward = its gradient (alignments.py:300-318 composed in
  *     reverse, D1-D4 in the reference): dW = grad[b] * (den - num marginals)
  *     (grad nullable = ones), from `state` and W alone.

@@ -109,6 +109,7 @@ struct CkArgs {
   float* nabd;             // [B,K+1,NPG] num alpha at chunk starts
   float* nbbd;             // [B,K+1,NPG] num beta at chunk starts
   float* cf;               // [B,T] frame offsets c_t = ceil(max W_t) (phase A's)
+  int* tab;                // [B,2,NPG] phase C's gather tables (boff, loff), written by the walks
   // hand-off words, tagged per call (no zeroing pass): a word carries this
   // call's tag or is not yet written in this call (an older call's tag, or
   // whatever the scratch held: a 62-bit / 40-bit random tag matches it with
@@ -189,7 +190,7 @@ LT_DEVINL float safe_max(float m) { return __builtin_isfinite(m) ? m : 0.f; }
 #define CK_ASTAMP(k)                                                                 \
   do {                                                                               \
     if (a.stamps && LT_ABL(a, 256) && (threadIdx.x & 63) == 0)                        \
-      a.stamps[(long long)a.B * a.K * 8 + (long long)id * 4 + (k)] =                  \
+      a.stamps[(long long)a.B * a.K * 8 + (long long)id * 8 + (k)] =                  \
           (long long)__builtin_amdgcn_s_memtime();                                   \
   } while (0)
 #else
@@ -646,6 +647,7 @@ LT_DEVINL void transfer_role(const CkArgs& a, int b, int k, int wave) {
   aissue(0);
   if (nt > 1) aissue(1);
   wait_vmcnt(nt > 1 ? a.a_ni : 0);
+  CK_ASTAMP(4);
   lds_frame<BF16, PPL, FULL>(aframe(0), fo, fr);
   for (int f = 0; f < nt; ++f) step(fr, f, f + 1 < nt);
   if (lane < nt) a.cf[(long long)b * a.T + t0 + lane] = cfl_lane;
@@ -697,6 +699,27 @@ LT_DEVINL unsigned long long poll_flag(const unsigned long long* p) {
   unsigned long long v;
   asm volatile("global_load_dwordx2 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
   return v;
+}
+// Loads for the head of a chunk's work, issued ahead of its LDS-DMA with no
+// wait of their own: the value is in the register only after a counted
+// wait_vmcnt (vector loads retire in order: the count is the number of vector
+// memory instructions the wave issued after the load) and landed(), which
+// keeps the compiler from reading the register above that wait. The compiler
+// does not count these loads, so it adds no vmcnt(0) of its own for them and
+// the DMA behind them stays in flight.
+LT_DEVINL unsigned long long early_flag(const unsigned long long* p) {
+  unsigned long long v;
+  asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(v) : "v"(p) : "memory");
+  return v;
+}
+LT_DEVINL float early_f32(const float* p) {
+  float v;
+  asm volatile("global_load_dword %0, %1, off" : "=v"(v) : "v"(p) : "memory");
+  return v;
+}
+template <class T>
+LT_DEVINL void landed(T& v) {
+  asm volatile("" : "+v"(v) : : "memory");
 }
 // a chunk's state in this call (0: not yet published)
 LT_DEVINL unsigned flag_state(unsigned long long v, unsigned long long tag) {
@@ -1029,6 +1052,22 @@ LT_DEVINL void num_walk(const CkArgs& a, int b, int lane, int nf, int Kl, int nl
   }
 }
 
+// Phase C's gather tables of utterance b, per string position, into the
+// state: boff clamped to 0 past the string (the reads are masked), loff -1
+// for "no arc". The labels are read where they lie (a short dependent scan
+// per position, once per utterance).
+LT_DEVINL void gather_tables(const CkArgs& a, int b, int tid, int nthr) {
+  const int* lab = a.labels + (long long)b * a.U;
+  int* boff = a.tab + (long long)b * 2 * a.NPG;
+  int* loff = boff + a.NPG;
+  for (int u = tid; u < a.NPG; u += nthr) {
+    int bo, lo;
+    string_offsets(a, lab, u, &bo, &lo);
+    boff[u] = bo < 0 ? 0 : bo;
+    loff[u] = lo;
+  }
+}
+
 // Utterance b's walks, one per wave, each following phase A's progress
 // through the ready flags (ChunkReady) when A runs in the same launch; `ph`
 // as above; `dyn` the launch's dynamic LDS (walk_lds).
@@ -1042,6 +1081,10 @@ LT_DEVINL void combine_role(const CkArgs& a, int b, int wave, unsigned char* dyn
   const int Kh = Kl / 2;                // the middle boundary (phases 1 and 2)
   const int V = a.V, C = a.C, CP = a.CP;
   const int nl = a.nlab[b];
+  // phase C's gather tables, once per utterance (every chunk of it stages
+  // them by one LDS-DMA instruction): before anything can end the walks, in
+  // the launch (or call) before phase C's, so plain stores
+  if (ph != kWalkRest) gather_tables(a, b, threadIdx.x, blockDim.x);
   if (ph == kWalkRest && a.uflag[b]) return;  // phase 1 sent it to the frame-serial kernels
   if (threadIdx.x == 0) *wl.bad = 0;
   __syncthreads();
@@ -1303,20 +1346,6 @@ __global__ __launch_bounds__(256) void ck_combine_kernel(const CkArgs a) {
                                  ck_dyn, a.half ? kWalkFirst : kWalkFull);
 }
 
-// Phase C's gather tables: per position, in LDS (labels staged by the whole
-// workgroup first).
-LT_DEVINL void gather_tables(const CkArgs& a, int b, int* lab, int* boff, int* loff, int tid,
-                             int nthr) {
-  for (int j = tid; j < a.U; j += nthr) lab[j] = a.labels[(long long)b * a.U + j];
-  __syncthreads();
-  for (int u = tid; u < a.NPG; u += nthr) {
-    int bo, lo;
-    string_offsets(a, lab, u, &bo, &lo);
-    boff[u] = bo < 0 ? 0 : bo;
-    loff[u] = lo;
-  }
-}
-
 // ---------------------------------------------------------------------------
 // C: local recursions + marginals -> dW (one workgroup per chunk)
 // ---------------------------------------------------------------------------
@@ -1400,9 +1429,7 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
   // chains of the workgroups sharing a CU need not sit on the same two SIMDs
   const int role = (wave + (int)(blockIdx.x >> 3)) & 3;
   const int hs = (nt + 1) / 2;  // den alpha forms E of frames [0, hs), den beta of [hs, nt)
-  // stage the chunk's live frames (all four waves)
   const long long off = e0 * (BF16 ? 2 : 4);
-  dma_issue(a.W, off, (long long)nt * cFB, lds_base_addr(lds), cNi, lane, wave, kMargWaves);
   unsigned char* wch = lds + (off & 15);
   float* xa = (float*)(lds + cOffAd);  // [L][CP] alpha_f, linear, max 1 (scale fs Ma)
   float* xb = (float*)(lds + cOffBd);  // [L][CP] beta_{f+1} of the core, linear, max 1
@@ -1412,7 +1439,6 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
   float* fs = (float*)(lds + a.c_off_fs);    // [L][kFs]
   int* boff = (int*)(lds + a.c_off_tab);
   int* loff = boff + NPG;
-  int* labs = loff + NPG;
   float* buf = (float*)(lds + a.c_off_buf) + 64 * wave;
   float* cfl = (float*)(lds + a.c_off_cf);
   int* fl = (int*)(lds + a.c_off_fl);
@@ -1433,35 +1459,66 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
       *cert_fail = 0;
     }
   };
-  if (tid < nt) cfl[tid] = a.cf[(long long)b * a.T + t0 + tid];
-  // phase 2's boundaries this chunk needs (alpha at k, beta at k + 1): one
-  // lane polls the walks' progress words before any wave's (sc1) loads of
-  // them, after the barriers below
-  if (a.cont && tid == 0) {
+  // The head: one memory round trip. Wave 0 issues everything the head needs
+  // that is not W -- the walks' progress words (one lane per word), the
+  // chunk's frame offsets, the utterance's gather tables (the walks wrote them
+  // to the state in the launch before this one; one LDS-DMA instruction to
+  // their home) -- ahead of its share of the chunk's W (LDS-DMA, all four
+  // waves), and waits for exactly those: vector loads retire in order, so with
+  // its W instructions still in flight (wait_vmcnt of their number) the small
+  // loads have landed, and the poll's verdict and the frame offsets are in LDS
+  // while W is still on its way. The one full wait is the staging barrier's;
+  // no compiler-visible load is issued between the first DMA and that wait.
+  // The tables' DMA instruction writes 1 KiB from the tables' home on, over
+  // the frame offsets' home and into the operand rows behind it (idle until
+  // the recursions): the offsets are stored after it has landed.
+  if (wave == 0) {
+    // phase 2's boundaries this chunk needs (alpha at k, beta at k + 1): the
+    // walks' progress words are read before any wave's (sc1) loads of the
+    // boundaries, which come after the barriers below. Word 0 / 1: den alpha
+    // / beta, 2 / 3: numerator alpha / beta.
     const int need_a = k - Kh, need_b = Kh - (k + 1);
     const unsigned long long* pg = a.prog + 4LL * b;
-    int ok = 1;
-    for (unsigned spins = 0;; ++spins) {
-      bool done = true;
-      if (need_a > 0)
-        done = (a.local || prog_count(poll_flag(pg + 0), a.pg_tag) >= need_a) &&
-               prog_count(poll_flag(pg + 2), a.pg_tag) >= need_a;
-      if (done && need_b > 0)
-        done = (a.local || prog_count(poll_flag(pg + 1), a.pg_tag) >= need_b) &&
-               prog_count(poll_flag(pg + 3), a.pg_tag) >= need_b;
-      if (done) break;
-      if (spins > kSpinMax) {  // phase 2 never ran (a placement that starves it)
-        ok = 0;
-        break;
+    unsigned long long pv = 0;
+    if (a.cont) pv = early_flag(pg + (lane & 3));
+    float cfv = early_f32(a.cf + (long long)b * a.T + t0 + min(lane, nt - 1));
+    dma_issue((const unsigned char*)a.tab, 8LL * b * NPG, 8LL * NPG,
+              lds_base_addr(lds + a.c_off_tab), 1, lane);
+    dma_issue(a.W, off, (long long)nt * cFB, lds_base_addr(lds), cNi, lane, 0, kMargWaves);
+    wait_vmcnt((cNi + kMargWaves - 1) / kMargWaves);  // this wave's W instructions stay in flight
+    landed(pv);
+    landed(cfv);
+    if (lane < nt) cfl[lane] = cfv;
+    if (a.cont) {
+      const int w = lane & 3, need = (w & 1) ? need_b : need_a;
+      const bool have = need <= 0 || (a.local && w < 2) || prog_count(pv, a.pg_tag) >= need;
+      int ok = 1;
+      // not yet: poll (the walks usually are far ahead, so this is the rare path)
+      if (__builtin_amdgcn_ballot_w64(!have) && tid == 0) {
+        for (unsigned spins = 0;; ++spins) {
+          bool done = true;
+          if (need_a > 0)
+            done = (a.local || prog_count(poll_flag(pg + 0), a.pg_tag) >= need_a) &&
+                   prog_count(poll_flag(pg + 2), a.pg_tag) >= need_a;
+          if (done && need_b > 0)
+            done = (a.local || prog_count(poll_flag(pg + 1), a.pg_tag) >= need_b) &&
+                   prog_count(poll_flag(pg + 3), a.pg_tag) >= need_b;
+          if (done) break;
+          if (spins > kSpinMax) {  // phase 2 never ran (a placement that starves it)
+            ok = 0;
+            break;
+          }
+          __builtin_amdgcn_s_sleep(2);
+        }
       }
-      __builtin_amdgcn_s_sleep(2);
+      if (tid == 0) fl[2 * cL + 2] = ok;
     }
     CK_STAMP(6);
-    fl[2 * cL + 2] = ok;
+  } else {
+    dma_issue(a.W, off, (long long)nt * cFB, lds_base_addr(lds), cNi, lane, wave, kMargWaves);
   }
-  gather_tables(a, b, labs, boff, loff, tid, blockDim.x);
   wait_vmcnt(0);
-  __syncthreads();
+  __syncthreads();  // W, the tables, cf and the poll's verdict for every wave
   if (a.cont && !fl[2 * cL + 2]) {
     if (tid == 0) a.uflag[b] = 1;
     return;
@@ -2021,7 +2078,7 @@ int al16(long long x) { return (int)((x + 15) & ~15LL); }
 
 struct CkLayout {
   // state (kept from lt_chunk_forward to lt_chunk_backward)
-  size_t uflag, lz, num, abd, bbd, nabd, nbbd, cf, mid, state;
+  size_t uflag, lz, num, abd, bbd, nabd, nbbd, cf, mid, tab, state;
   // scratch: forward = records + numerator bands; backward = the fallback's checkpoints
   size_t ready, rec, nb, f_alpha, f_an, f_loss, f_lz, f_num, f_side, scratch;
 };
@@ -2101,6 +2158,7 @@ int ck_plan(const lt_problem* pb, int local_norm, CkArgs* a, CkLayout* w) {
   w->nbbd = o; o += up256(4 * B * (K + 1) * a->NPG);
   w->cf = o; o += up256(4 * B * T);
   w->mid = o; o += up256(8 * B);
+  w->tab = o; o += up256(8 * B * a->NPG);  // 8 NPG bytes an utterance: whole 16-byte granules
   w->state = o;
   size_t s = 0;
   w->ready = s; s += up256(8LL * B * K + 32LL * B);  // ready flags, then the progress words
@@ -2131,6 +2189,7 @@ void ck_bind(CkArgs* a, const CkLayout& w, void* state, void* scratch) {
   a->nbbd = (float*)(st + w.nbbd);
   a->cf = (float*)(st + w.cf);
   a->mid = (float*)(st + w.mid);
+  a->tab = (int*)(st + w.tab);
   a->rec = sc ? (float*)(sc + w.rec) : nullptr;
   a->nb = sc ? (float*)(sc + w.nb) : nullptr;
   a->ready = sc ? (unsigned long long*)(sc + w.ready) : nullptr;
