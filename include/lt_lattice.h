@@ -494,5 +494,7 @@ const char* lt_version(void);
 #include "lt_expect.h"
 /* Per-label emission posteriors of a label string, likewise. */
 #include "lt_posterior.h"
+/* Expected values over the alignments of a label string, likewise. */
+#include "lt_string_expect.h"
 
 #endif /* LT_LATTICE_H_ */

@@ -95,6 +95,9 @@ _SIG = {
     'lt_table_align': [_G, _TP] + [_P] * 8 + [ctypes.c_size_t, _P],
     'lt_table_align_posteriors_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_align_posteriors': [_G, _TP] + [_P] * 7 + [ctypes.c_size_t, _P],
+    'lt_table_align_expectation_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
+    'lt_table_align_expectation': [_G, _TP] + [_P] * 13 + [ctypes.c_size_t, _P],
+    'lt_table_string_scatter': [_G, _TP] + [_P] * 7,
     'lt_table_sample_workspace_bytes': [_G, _TP, _I32, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_sample': [_G, _TP, _P, _P, _P, _P, _I32, ctypes.c_uint64, _P, _P, _P,
                         ctypes.c_size_t, _P],
@@ -126,14 +129,18 @@ _SIG = {
 # the functions each header of the C ABI declares: include/lt_align.h (forced
 # alignment), include/lt_sample.h (path sampling), include/lt_expect.h
 # (posterior means of arc values), include/lt_posterior.h (emission posteriors
-# of a label string) and include/lt_lattice.h (everything else)
+# of a label string), include/lt_string_expect.h (expected values over a label
+# string's alignments, the string scatter) and include/lt_lattice.h (everything
+# else)
 EXPORTED_ALIGN = ('lt_table_align_workspace_bytes', 'lt_table_align')
 EXPORTED_SAMPLE = ('lt_table_sample_workspace_bytes', 'lt_table_sample')
 EXPORTED_EXPECT = ('lt_table_expectation_workspace_bytes', 'lt_table_expectation')
 EXPORTED_POSTERIOR = ('lt_table_align_posteriors_workspace_bytes', 'lt_table_align_posteriors')
+EXPORTED_ALIGN_EXPECT = ('lt_table_align_expectation_workspace_bytes',
+                         'lt_table_align_expectation', 'lt_table_string_scatter')
 EXPORTED = (tuple(n for n in _SIG
                   if n not in (EXPORTED_ALIGN + EXPORTED_SAMPLE + EXPORTED_EXPECT +
-                               EXPORTED_POSTERIOR)) +
+                               EXPORTED_POSTERIOR + EXPORTED_ALIGN_EXPECT)) +
             ('lt_last_error', 'lt_version'))
 
 
@@ -704,6 +711,78 @@ def table_align_posteriors(graph, W, num_frames, labels, num_labels):
                                          _ptr(emission), _ptr(log_prob), _ptr(ws), nbytes.value,
                                          _stream()), 'lt_table_align_posteriors')
   return emission, log_prob
+
+
+def table_align_expectation_supported(graph, W, labels):
+  """Whether lt_table_align_expectation (and lt_table_string_scatter) takes
+  this problem (FrameDependent, U <= 255): a host-only query, no launch. Other
+  errors raise."""
+  pb = _tproblem(graph, W, labels.shape[-1])
+  nbytes = ctypes.c_size_t(0)
+  rc = lib().lt_table_align_expectation_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
+                                                        ctypes.byref(nbytes))
+  if rc == LT_EUNSUPPORTED:
+    return False
+  _check(rc, 'lt_table_align_expectation_workspace_bytes')
+  return True
+
+
+def table_align_expectation(graph, W, lexical_values, blank_values, num_frames, labels,
+                            num_labels, want_post=True, want_cov=True):
+  """lt_table_align_expectation, one launch: (expected [B], log_prob [B],
+  emission [B,T,U], blank_occ [B,T,U+1], cov_lex [B,T,U], cov_blank [B,T,U+1])
+  for values in string coordinates (lexical_values [B,T,U], blank_values
+  [B,T,U+1]); all fp32. The posteriors (emission, blank_occ: d expected / d
+  values = d log_prob / d string weights) are None without want_post, the
+  covariances (d expected / d string weights) without want_cov; neither wanted
+  is the value-only call. Raises LatticeLibraryError (LT_EUNSUPPORTED) for
+  FrameLabelDependent graphs or past U = 255."""
+  pb = _tproblem(graph, W, labels.shape[-1])
+  B, T = W.shape[:2]
+  U = labels.shape[-1]
+  if tuple(lexical_values.shape) != (B, T, U) or tuple(blank_values.shape) != (B, T, U + 1):
+    raise ValueError(f'lexical_values {tuple(lexical_values.shape)} / blank_values '
+                     f'{tuple(blank_values.shape)} do not match [{B}, {T}, {U}] / '
+                     f'[{B}, {T}, {U + 1}]')
+  lexical_values = lexical_values.to(device=W.device, dtype=torch.float32).contiguous()
+  blank_values = blank_values.to(device=W.device, dtype=torch.float32).contiguous()
+  nbytes = ctypes.c_size_t(0)
+  _check(lib().lt_table_align_expectation_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
+                                                          ctypes.byref(nbytes)),
+         'lt_table_align_expectation_workspace_bytes')
+  ws = (torch.empty([nbytes.value], dtype=torch.uint8, device=W.device)
+        if nbytes.value and (want_post or want_cov) else None)
+  expected, log_prob = _f32([B], W), _f32([B], W)
+  emission = _f32([B, T, U], W) if want_post else None
+  blank_occ = _f32([B, T, U + 1], W) if want_post else None
+  cov_lex = _f32([B, T, U], W) if want_cov else None
+  cov_blank = _f32([B, T, U + 1], W) if want_cov else None
+  _check(lib().lt_table_align_expectation(
+      ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W), _ptr(lexical_values), _ptr(blank_values),
+      _ptr(num_frames), _ptr(labels), _ptr(num_labels), _ptr(expected), _ptr(log_prob),
+      _ptr(emission), _ptr(blank_occ), _ptr(cov_lex), _ptr(cov_blank), _ptr(ws),
+      nbytes.value if ws is not None else 0, _stream()), 'lt_table_align_expectation')
+  return expected, log_prob, emission, blank_occ, cov_lex, cov_blank
+
+
+def table_string_scatter(graph, W, g_lex, g_blank, num_frames, labels, num_labels):
+  """lt_table_string_scatter: the dense fp32 dW [B,T,C,V+1] (W's shape) of
+  string-coordinate gradients g_lex [B,T,U] / g_blank [B,T,U+1]: the memset and
+  one kernel, positions that share a cell summed in a fixed order."""
+  pb = _tproblem(graph, W, labels.shape[-1])
+  B, T = W.shape[:2]
+  U = labels.shape[-1]
+  if tuple(g_lex.shape) != (B, T, U) or tuple(g_blank.shape) != (B, T, U + 1):
+    raise ValueError(f'g_lex {tuple(g_lex.shape)} / g_blank {tuple(g_blank.shape)} do not match '
+                     f'[{B}, {T}, {U}] / [{B}, {T}, {U + 1}]')
+  g_lex = g_lex.to(device=W.device, dtype=torch.float32).contiguous()
+  g_blank = g_blank.to(device=W.device, dtype=torch.float32).contiguous()
+  dW = _f32(tuple(W.shape), W)
+  _check(lib().lt_table_string_scatter(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(g_lex),
+                                       _ptr(g_blank), _ptr(num_frames), _ptr(labels),
+                                       _ptr(num_labels), _ptr(dW), _stream()),
+         'lt_table_string_scatter')
+  return dW
 
 
 def table_sample(graph, W, num_frames, log_z, alpha, num_samples, seed):

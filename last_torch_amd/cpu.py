@@ -4,9 +4,10 @@
 the HIP kernels (liblt_lattice.so) when they live on a ROCm device: the
 device of the tensors picks the implementation, as in the reference, and
 there is no fallback from one to the other (a ROCm tensor never runs on the
-host; a missing HIP library raises). The one function here that also takes
-ROCm tensors is align_posteriors, which then runs its torch ops on their
-device: RecognitionLattice.align_posteriors past its kernel's range.
+host; a missing HIP library raises). The two functions here that also take
+ROCm tensors are align_posteriors and align_expectation, which then run their
+torch ops on that device: RecognitionLattice.align_posteriors and
+align_expectation past their kernels' range.
 
 One formulation covers both alignment lattices and any context dependency.
 A frame of FrameDependent (K = 0) or FrameLabelDependent(K) is
@@ -35,6 +36,10 @@ MaxTropical's first-argmax rule prefers the blank, then fewer expansions.
   align_posteriors (not in the reference) emission posteriors of the label
                                       string: the Log string distance
                                       differentiated w.r.t. the same weights
+  align_expectation (not in the reference) posterior mean, over the string's
+                                      alignments, of a path value in string
+                                      coordinates (lt_string_expect.h): the
+                                      same derivative kept in the graph
   sample        (not in the reference) paths from the posterior exp(w) / Z:
                                       Gumbel-max on Philox4x32-10, walked
                                       backwards over alpha (lt_sample.h)
@@ -273,6 +278,55 @@ def align_posteriors(W: torch.Tensor, nf: torch.Tensor, labels: torch.Tensor, nl
     emission = torch.where(fin[:, None, None], grad, emission)
   log_prob = torch.where(fin, dist, torch.full_like(dist, -torch.inf))
   return emission, log_prob
+
+
+def align_expectation(W: torch.Tensor, nf: torch.Tensor, labels: torch.Tensor, nl: torch.Tensor,
+                      context: contexts.ContextDependency, alignment,
+                      lexical_values: torch.Tensor, blank_values: torch.Tensor):
+  """(expected [B], log_prob [B]) of include/lt_string_expect.h: the posterior
+  mean, over the alignments of the label string, of a path value given in
+  string coordinates (lexical_values [B, T, U] for the arc leaving position u
+  on frame t, blank_values [B, T, U+1] for the blank arc at position u).
+  align_posteriors' construction kept in the graph: the Log string distance is
+  differentiated with respect to the string's own lexical and blank weights
+  (string_weights, with its graph to W) with create_graph, and expected is the
+  sum of those derivatives (emission, blank_occ) times the values. So expected
+  and log_prob are differentiable w.r.t. W, and expected w.r.t. the values, by
+  ordinary autograd (d expected / dW is a second derivative of log_prob).
+  FrameLabelDependent: the derivative sums a frame's expansion slots. Runs in
+  W's dtype on W's device. Edge rules: a value where the derivative is 0 (an
+  arc of weight -inf, rows t >= nf, columns past nl) is not read into the
+  arithmetic; an utterance whose distance is not finite is masked out of the
+  differentiated sum: log_prob = -inf, expected = 0, zero gradients."""
+  K = expansions(alignment)
+  B = W.shape[0]
+  V = W.shape[-1] - 1
+  lab = labels.long()
+  lab = torch.where((lab >= 1) & (lab <= V), lab, torch.zeros_like(lab))
+  wants_graph = torch.is_grad_enabled() and (W.requires_grad or lexical_values.requires_grad or
+                                             blank_values.requires_grad)
+  with torch.enable_grad():
+    blank, lex = string_weights(W, lab, context)
+    if not blank.requires_grad:
+      blank, lex = blank.detach().requires_grad_(), lex.detach().requires_grad_()
+    dist = _string_distance(blank, lex, nf, nl, K, semirings.Log)
+    fin = torch.isfinite(dist.detach())
+    total = torch.where(fin, dist, torch.zeros_like(dist)).sum()
+    g_lex, g_blank = (torch.autograd.grad(total, [lex, blank], create_graph=True,
+                                          allow_unused=True)
+                      if total.requires_grad else (None, None))
+    expected = torch.zeros([B], dtype=W.dtype, device=W.device)
+    for g, val in ((g_lex, lexical_values), (g_blank, blank_values)):
+      if g is None or g.numel() == 0:
+        continue
+      val = val.to(device=W.device, dtype=W.dtype)
+      expected = expected + (g * torch.where(g.detach() != 0, val, torch.zeros_like(val))).sum(
+          dim=(1, 2))
+    expected = torch.where(fin, expected, torch.zeros_like(expected))
+    log_prob = torch.where(fin, dist, torch.full_like(dist, -torch.inf).detach())
+  if not wants_graph:
+    expected, log_prob = expected.detach(), log_prob.detach()
+  return expected, log_prob
 
 
 def expectation(W: torch.Tensor, values: torch.Tensor, nf: torch.Tensor,

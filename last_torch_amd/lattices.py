@@ -21,6 +21,11 @@ weights once through the ``WeightFn`` plugin as a contiguous
   align_posteriors -> lt_table_align_posteriors (emission posteriors of the
                      label string; not in the reference); past its range the
                      torch restatement (cpu.align_posteriors) on the device
+  align_expectation -> lt_table_align_expectation (expected value of a path
+                     quantity over the transcript's alignments, with the
+                     posteriors and covariances its backward needs; not in the
+                     reference) + lt_table_string_scatter in the backward; past
+                     its range cpu.align_expectation on the device
   sample          -> lt_den_forward / lt_table_forward (Log) + lt_table_sample
                      (paths from the posterior; not in the reference)
   expectation     -> lt_table_expectation (posterior mean of arc values with
@@ -268,6 +273,47 @@ class _ExpectFn(torch.autograd.Function):
     if need_v:
       dv = (g_e * marg).to(values.dtype)
     return dW, dv, None, None
+
+
+class _AlignExpectFn(torch.autograd.Function):
+  """(expected, log_prob) of include/lt_string_expect.h: the forward is ONE
+  lt_table_align_expectation call that also writes what the inputs' gradients
+  need (the posteriors emission / blank_occ = d expected / d values = d
+  log_prob / d string weights, the covariances = d expected / d string
+  weights); the backward combines them with the incoming gradients in string
+  coordinates and ONE lt_table_string_scatter call makes the dense dW. A
+  second backward (retain_graph) recomputes them. Not twice differentiable."""
+
+  @staticmethod
+  def forward(ctx, W, lv, bv, nf, lab, nl, graph):
+    need_w, need_l, need_b = ctx.needs_input_grad[:3]
+    expected, log_prob, *grads = _native.table_align_expectation(
+        graph, W, lv, bv, nf, lab, nl, want_post=need_w or need_l or need_b, want_cov=need_w)
+    ctx.graph, ctx.grads = graph, grads
+    ctx.save_for_backward(W, lv, bv, nf, lab, nl)
+    return expected, log_prob
+
+  @staticmethod
+  def backward(ctx, g_e, g_lp):
+    W, lv, bv, nf, lab, nl = ctx.saved_tensors
+    need_w, need_l, need_b = ctx.needs_input_grad[:3]
+    grads, ctx.grads = ctx.grads, None
+    if grads is None and (need_w or need_l or need_b):  # a second backward through the same graph
+      grads = _native.table_align_expectation(ctx.graph, W, lv, bv, nf, lab, nl, want_post=True,
+                                              want_cov=need_w)[2:]
+    emission, blank_occ, cov_lex, cov_blank = grads if grads is not None else [None] * 4
+    g_e = g_e.float()[:, None, None]
+    dW = dl = db = None
+    if need_w:
+      g_lp = g_lp.float()[:, None, None]
+      dW = _native.table_string_scatter(ctx.graph, W, g_e * cov_lex + g_lp * emission,
+                                        g_e * cov_blank + g_lp * blank_occ, nf, lab,
+                                        nl).to(W.dtype)
+    if need_l:
+      dl = (g_e * emission).to(lv.dtype)
+    if need_b:
+      db = (g_e * blank_occ).to(bv.dtype)
+    return dW, dl, db, None, None, None, None
 
 
 class _TableNumFn(torch.autograd.Function):
@@ -620,6 +666,90 @@ class RecognitionLattice(nn.Module, Generic[T]):
     emission, log_prob = out
     T_, U_ = W.shape[1], lab.shape[-1]
     return (self._home(emission.float().reshape(*batch_dims, T_, U_), frames),
+            self._home(log_prob.float().reshape(batch_dims), frames))
+
+  def align_expectation(self, frames: torch.Tensor, num_frames: torch.Tensor,
+                        labels: torch.Tensor, num_labels: torch.Tensor,
+                        lexical_values: torch.Tensor,
+                        blank_values: Optional[torch.Tensor] = None, cache: Optional[T] = None):
+    """Expected value of a path quantity over the alignments of a transcript
+    (not in the reference): `expectation`'s question on the lattice
+    intersected with the label string, differentiable, so it can be a loss
+    term -- expected emission delay (lexical_values[t, u] = t), expected
+    alignment cost against reference timestamps, the alignment entropy of one
+    transcript (the string's own weights as values: log_prob - expected). The
+    definition is in include/lt_string_expect.h. Values are given in string
+    coordinates, the coordinates of `align_posteriors`:
+
+        lexical_values [batch..., T, U]    the arc leaving string position u
+                                           (the one that emits labels[u]) on frame t
+        blank_values   [batch..., T, U+1]  the blank arc at position u on frame t
+                                           (None: zeros)
+
+        expected = sum_pi p(pi) sum_{a in pi} v_a,  p(pi) = exp(w(pi) - log_prob)
+                 = sum_{t,u} emission[t,u] lexical_values[t,u]
+                 + sum_{t,u} blank_occ[t,u] blank_values[t,u]
+
+    over the alignment paths pi of the transcript, emission as
+    `align_posteriors` returns it and blank_occ the same posterior of the
+    blank arcs. Values may have any sign. Labels outside 1..V are epsilons.
+
+    Returns (expected [batch...], log_prob [batch...]). Both are
+    differentiable w.r.t. the weight function through the arc weights
+    (d expected / d w_a is the covariance of the arc indicator with the path
+    value), and `expected` also w.r.t. both value tensors: d expected / d
+    lexical_values = emission, d expected / d blank_values = blank_occ. On
+    ROCm tensors the gradients come from the forward's one
+    lt_table_align_expectation call plus one lt_table_string_scatter call in
+    the backward (FrameDependent, U <= 255, fp32 or bf16 weights) and are not
+    twice differentiable; FrameLabelDependent or longer strings run
+    cpu.align_expectation (plain autograd) on the tensors' own device; CPU
+    tensors run it on the host. An arc of weight -inf contributes nothing and
+    its value is ignored (NaN or inf there is harmless), as are values on
+    frames t >= num_frames and positions past num_labels; an utterance whose
+    log_prob is not finite (no path, -inf arcs on every path, num_labels
+    outside [0, U]) gives log_prob = -inf, expected = 0 and zero gradients,
+    never NaN; num_frames = 0 with num_labels = 0 gives (0, 0)."""
+    batch_dims = tuple(num_frames.shape)
+    if tuple(frames.shape[:-2]) != batch_dims:
+      raise ValueError('frames and num_frames have different batch_dims: '
+                       f'{tuple(frames.shape[:-2])} vs {batch_dims}')
+    if tuple(labels.shape[:-1]) != batch_dims:
+      raise ValueError('labels and num_frames have different batch_dims: '
+                       f'{tuple(labels.shape[:-1])} vs {batch_dims}')
+    if tuple(num_labels.shape) != batch_dims:
+      raise ValueError('num_labels and num_frames have different batch_dims: '
+                       f'{tuple(num_labels.shape)} vs {batch_dims}')
+    W, nf, batch_dims, B, _, _, _ = self._prepare(cache, frames, num_frames)
+    lab = torch.as_tensor(labels).reshape(B, -1).to(device=W.device, dtype=torch.int32).contiguous()
+    nl = _lengths(num_labels, B, W.device)
+    T_, U_ = W.shape[1], lab.shape[-1]
+    lv = torch.as_tensor(lexical_values)
+    if tuple(lv.shape) != (*batch_dims, T_, U_):
+      raise ValueError(f'lexical_values should have the shape {(*batch_dims, T_, U_)}, but got '
+                       f'{tuple(lv.shape)}')
+    if blank_values is None:
+      bv = torch.zeros([B, T_, U_ + 1], dtype=torch.float32, device=W.device)
+    else:
+      bv = torch.as_tensor(blank_values)
+      if tuple(bv.shape) != (*batch_dims, T_, U_ + 1):
+        raise ValueError(f'blank_values should have the shape {(*batch_dims, T_, U_ + 1)}, but '
+                         f'got {tuple(bv.shape)}')
+    lv = lv.to(W.device).reshape(B, T_, U_)
+    bv = bv.to(W.device).reshape(B, T_, U_ + 1)
+    if W.device.type == 'cpu':
+      out = cpu.align_expectation(W, nf, lab, nl.long(), self.context, self.alignment, lv, bv)
+    else:
+      graph = self._graph(W.device)
+      if _native.table_align_expectation_supported(graph, W, lab):
+        out = _AlignExpectFn.apply(W, lv, bv, nf, lab, nl, graph)
+      else:
+        # the restatement on the device: the walk reads the graph's device copy
+        # of the next-state table, nothing visits the host
+        out = cpu.align_expectation(W.float(), nf.long(), lab, nl.long(),
+                                    contexts.NextStateTable(graph.table), self.alignment, lv, bv)
+    expected, log_prob = out
+    return (self._home(expected.float().reshape(batch_dims), frames),
             self._home(log_prob.float().reshape(batch_dims), frames))
 
   def sample(self, frames: torch.Tensor, num_frames: torch.Tensor, num_samples: int, seed: int,
