@@ -26,7 +26,10 @@
 //      frames reach the wave through its own two-slot LDS ring (LDS-DMA, a
 //      frame issued two steps ahead). Also the numerator's group bands (the
 //      string lattice's frame steps composed over kGrp frames, a step of
-//      their own beside the frame's product) and the frame offsets.
+//      their own beside the frame's product) and the frame offsets. For
+//      V = 32 and fp32 W the frame geometry and the frame's position in the
+//      chunk are compile-time constants (transfer_role's SPEC form); every
+//      other case takes the run-time form.
 //   B  one workgroup per utterance: the den alpha / beta vectors at every
 //      chunk boundary (K steps of a 33 x 33 log-semiring vector-matrix
 //      product each), the numerator alpha / beta over the groups with the
@@ -244,6 +247,44 @@ LT_DEVINL void dma_issue(const unsigned char* base, long long off, long long byt
   }
 }
 
+// Phase A's compile-time geometry (fp32 W at V = 32): the frame, its DMA
+// count and its last 16-byte granule. 4356 = 16 * 272 + 4 and a frame starts
+// on a multiple of 4 bytes, so whatever (off & 15) is, the copy that starts at
+// the granule holding `off` spans granules 0 .. 272: kANi wave instructions.
+constexpr int kAFb = 33 * 33 * 4;
+constexpr int kANi = 5;
+constexpr int kALastG = (12 + kAFb + 15) / 16 - 1;
+static_assert((kAFb + 15) / 16 - 1 == kALastG && kALastG >= 64 * (kANi - 1) &&
+                  kALastG < 64 * kANi,
+              "the frame's last granule belongs to the last DMA instruction for every alignment");
+// dma_issue for that frame, straight line: `gbase` (wave-uniform, SGPRs) is
+// the granule holding the frame's first byte, v0 = 16 * lane, v4 = 16 *
+// min(256 + lane, kALastG) (the last-granule clamp). The instruction offset
+// moves the global and the LDS address alike; the fifth instruction has no
+// offset field wide enough, so M0 moves instead. M0 is saved and restored as
+// in glds16. (s_nop 4: an SGPR base the compiler restored through a VALU
+// read needs five states before a vector memory instruction reads it.)
+LT_DEVINL void dma_frame_f32v32(const unsigned char* gbase, unsigned v0, unsigned v4,
+                                unsigned lds_addr) {
+  static_assert(kANi == 5, "five instructions written out");
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %4\n\t"
+      "s_nop 4\n\t"
+      "global_load_lds_dwordx4 %2, %1\n\t"
+      "global_load_lds_dwordx4 %2, %1 offset:1024\n\t"
+      "global_load_lds_dwordx4 %2, %1 offset:2048\n\t"
+      "global_load_lds_dwordx4 %2, %1 offset:3072\n\t"
+      "s_mov_b32 m0, %5\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %3, %1\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "s"(gbase), "v"(v0), "v"(v4), "s"(lds_addr), "s"(lds_addr + 4096u)
+      : "memory");
+}
+
 // wave-uniform max / sum over all 64 lanes with DPP only (no LDS round trip):
 // butterflies inside each row of 16, then row_bcast:15 / row_bcast:31 fold
 // rows 0-1 into 2-3, and lane 63 holds the total. Every stage is one
@@ -418,8 +459,19 @@ LT_DEVINL void st_wt4(__amdgpu_buffer_rsrc_t r, int idx, float x, float y, float
 // far-below-max weight, which only the relaxed path takes, under phase C's
 // per-frame certificate; 2: a NaN / +inf weight or an all -inf frame, always
 // the frame-serial kernels); phase B polls it (ChunkReady).
-template <bool BF16, int PPL, bool FULL>
+//
+// SPEC (fp32 W at V = 32, chunks of at most kASpecL frames; ck_kernel_ab picks
+// it where the plan's geometry is the one baked in here): the frame size, the
+// DMA count and the counted wait are immediates, a frame's DMA is
+// dma_frame_f32v32 on an address carried from the chunk's first frame, and
+// the step is instantiated per frame position behind one f < nt guard each,
+// so the band triangle, the group index and its store, the ring slot and
+// lane == f are constants and a frame's band chains share one block. Same
+// operations in the same order as the run-time form: same bits.
+constexpr int kASpecL = 8;
+template <bool BF16, int PPL, bool FULL, bool SPEC>
 LT_DEVINL void transfer_role(const CkArgs& a, int b, int k, int wave) {
+  static_assert(!SPEC || (FULL && !BF16), "the specialised phase A is fp32 at V = 32");
   __shared__ __attribute__((aligned(16))) float s_rt[4][32];
   __shared__ __attribute__((aligned(16))) float s_dg[4][32];
   __shared__ int s_lab[4][128];
@@ -477,13 +529,40 @@ LT_DEVINL void transfer_role(const CkArgs& a, int b, int k, int wave) {
   unsigned char* aring = ck_dyn + wave * 2 * kASlot;
   float cfl_lane = 0.f;  // lane f holds frame f's offset
   auto goff = [&](int f) { return ((long long)b * a.T + t0 + f) * a.FB; };
+  // SPEC: the chunk's first frame (its granule in SGPRs, its offset inside
+  // it); frame f starts kAFb * f bytes on, f a constant at every use
+  const long long g0 = SPEC ? goff(0) : 0;
+  const int q0 = (int)(g0 & 15);
+  const unsigned long long wb = SPEC ? (unsigned long long)(uintptr_t)(a.W + (g0 - q0)) : 0;
+  const unsigned char* const wbase =
+      SPEC ? (const unsigned char*)(uintptr_t)(
+                 (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)wb) |
+                 (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(wb >> 32))
+                     << 32)
+           : nullptr;
+  const unsigned ring_addr = SPEC ? __builtin_amdgcn_readfirstlane(lds_base_addr(aring)) : 0;
+  const unsigned dv0 = 16u * lane, dv4 = 16u * min(64 * (kANi - 1) + lane, kALastG);
   auto aissue = [&](int f) {
     dma_issue(a.W, goff(f), a.FB, lds_base_addr(aring) + (unsigned)((f & 1) * kASlot), a.a_ni, lane);
   };
   auto aframe = [&](int f) -> const unsigned char* {
     return aring + (f & 1) * kASlot + (int)(goff(f) & 15);
   };
-  auto step = [&](FrameRegs<BF16, PPL>& F, int f, bool reload) {
+  auto sissue = [&](int f) __attribute__((always_inline)) {
+    dma_frame_f32v32(wbase + ((q0 + kAFb * f) & ~15), dv0, dv4,
+                     ring_addr + (unsigned)((f & 1) * kASlot));
+  };
+  auto sframe = [&](int f) __attribute__((always_inline)) -> const unsigned char* {
+    return aring + (f & 1) * kASlot + ((q0 + kAFb * f) & 15);
+  };
+  // the counted wait that leaves one frame's DMA in flight (more) or none
+  // (SPEC; the run-time form is wait_vmcnt(more ? a.a_ni : 0))
+  auto await = [&](bool more) __attribute__((always_inline)) {
+    static_assert(kANi == 5, "the immediate below");
+    if (more) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  };
+  auto step = [&](FrameRegs<BF16, PPL>& F, int f, bool reload) __attribute__((always_inline)) {
     mask_frame<BF16, PPL, FULL>(V, lane, boff, loff, F);
     // numerator: band step over the group (positions past the string read -inf)
     // (diagnostic builds: LT_CK_DBG bit 1024 skips it -- timing only)
@@ -526,9 +605,11 @@ LT_DEVINL void transfer_role(const CkArgs& a, int b, int k, int wave) {
     }
     // frame f + 2 into the slot frame f came through (its reads into F have
     // returned: F was just used)
-    if (f + 2 < nt && !LT_ABL(a, 8192)) {
+    // (SPEC: positions kASpecL - 2 on have no frame two steps ahead)
+    if (f + 2 < nt && (!SPEC || f + 2 < kASpecL) && !LT_ABL(a, 8192)) {
       __builtin_amdgcn_s_waitcnt(0xc07f);
-      aissue(f + 2);
+      if constexpr (SPEC) sissue(f + 2);
+      else aissue(f + 2);
     }
     // the frame's offset c = ceil(max W log2 e), an integer in log2 units
     // (masked values are -inf), so every sum of offsets is exact
@@ -582,8 +663,9 @@ LT_DEVINL void transfer_role(const CkArgs& a, int b, int k, int wave) {
     // step f - 1; only frame f + 2's (issued at the start of this step)
     // may still be in flight
     if (reload && !LT_ABL(a, 8192)) {
-      wait_vmcnt(f + 2 < nt ? a.a_ni : 0);
-      lds_frame<BF16, PPL, FULL>(aframe(f + 1), fo, F);
+      if constexpr (SPEC) await(f + 2 < nt);
+      else wait_vmcnt(f + 2 < nt ? a.a_ni : 0);
+      lds_frame<BF16, PPL, FULL>(SPEC ? sframe(f + 1) : aframe(f + 1), fo, F);
     }
 
     // state-0 row: r' = p00 * e0 + r Ec (VALU, beside the MFMAs), scaled by
@@ -644,12 +726,25 @@ LT_DEVINL void transfer_role(const CkArgs& a, int b, int k, int wave) {
   // bytes a lane, a_ni wave instructions a frame) and into F one step ahead:
   // frame f + 2's DMA is issued at the start of step f, so every frame has
   // more than a step to land, with no registers held for it
-  aissue(0);
-  if (nt > 1) aissue(1);
-  wait_vmcnt(nt > 1 ? a.a_ni : 0);
+  if constexpr (SPEC) {
+    sissue(0);
+    if (nt > 1) sissue(1);
+  } else {
+    aissue(0);
+    if (nt > 1) aissue(1);
+  }
+  if constexpr (SPEC) await(nt > 1);
+  else wait_vmcnt(nt > 1 ? a.a_ni : 0);
   CK_ASTAMP(4);
-  lds_frame<BF16, PPL, FULL>(aframe(0), fo, fr);
-  for (int f = 0; f < nt; ++f) step(fr, f, f + 1 < nt);
+  lds_frame<BF16, PPL, FULL>(SPEC ? sframe(0) : aframe(0), fo, fr);
+  if constexpr (SPEC) {
+    // nt <= L <= kASpecL: one copy of the step per frame position
+#pragma unroll
+    for (int f = 0; f < kASpecL; ++f)
+      if (f < nt) step(fr, f, f + 1 < kASpecL && f + 1 < nt);
+  } else {
+    for (int f = 0; f < nt; ++f) step(fr, f, f + 1 < nt);
+  }
   if (lane < nt) a.cf[(long long)b * a.T + t0 + lane] = cfl_lane;
   CK_ASTAMP(2);
 
@@ -1315,7 +1410,7 @@ constexpr int kWalkDc = PPL == 1 ? 4 : 3;
 // the stretch they can follow A's front. Dispatch order is not assumed for
 // correctness: a walk that never sees its chunk times out to the
 // frame-serial kernels.
-template <bool BF16, int PPL, bool FULL>
+template <bool BF16, int PPL, bool FULL, bool SPEC = false>
 __global__ __launch_bounds__(256, kAbWaves) void ck_ab_kernel(const CkArgs a) {
   const int nc = a.nc;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1336,7 +1431,7 @@ __global__ __launch_bounds__(256, kAbWaves) void ck_ab_kernel(const CkArgs a) {
   const int Kl = (nf + a.L - 1) / a.L;
   const int k = r < a.B ? m : Kl - 1 - m;
   if (r < a.B ? m > Kl - 1 - m : Kl - 1 - m <= m) return;  // past the middle (or no chunk)
-  transfer_role<BF16, PPL, FULL>(a, b, k, wave);
+  transfer_role<BF16, PPL, FULL, SPEC>(a, b, k, wave);
 }
 
 template <int PPL>
@@ -2220,7 +2315,20 @@ int ck_check(const lt_problem* pb) {
   return LT_OK;
 }
 
-const void* ck_kernel_ab(int ppl, bool bf16, bool full) {
+// 1: the last ck_ab_kernel launch took the specialised phase A; the
+// diagnostic build exports it for the tests
+int g_last_ab_spec = 0;
+// LT_CHUNK_GENERIC=1 (read per call) forces the run-time phase A as it forces
+// the run-time phase C (ck_kernel_c)
+const void* ck_kernel_ab(int ppl, bool bf16, bool full, const CkArgs& a) {
+  g_last_ab_spec = 0;
+  // the specialised phase A must be the plan's: frame size, DMA count, V, L
+  if (full && !bf16 && a.V == 32 && a.FB == kAFb && a.a_ni == kANi && a.L <= kASpecL &&
+      ck_env("LT_CHUNK_GENERIC", 0) == 0) {
+    g_last_ab_spec = 1;
+    return ppl == 1 ? (const void*)ck_ab_kernel<false, 1, true, true>
+                    : (const void*)ck_ab_kernel<false, 2, true, true>;
+  }
   if (full)
     return ppl == 1 ? (bf16 ? (const void*)ck_ab_kernel<true, 1, true>
                             : (const void*)ck_ab_kernel<false, 1, true>)
@@ -2288,7 +2396,7 @@ int ck_launch_ab(CkArgs& a, bool bf16, hipStream_t st) {
   const long long nwa = (items + 3) / 4;
   const int at = ck_env("LT_CHUNK_WALK_AT", std::max(0, 100 - 4800 / std::max(a.B, 1)));
   a.wpos = (int)(nwa * std::min(std::max(at, 0), 100) / 100);
-  int rc = ck_launch(ck_kernel_ab(a.PPL, bf16, a.V == 32), (int)(a.nc + nwa),
+  int rc = ck_launch(ck_kernel_ab(a.PPL, bf16, a.V == 32, a), (int)(a.nc + nwa),
                      std::max(fuse ? kWalkLdsBytes : 0, kALdsBytes), st, a);
   if (rc || fuse) return rc;
   return ck_launch(ck_kernel_b(a.PPL), a.B, kWalkLdsBytes, st, a);
@@ -2348,6 +2456,8 @@ int ck_lds_c(const CkArgs& a, bool bf16) {
 #ifdef LT_DIAG
 // diagnostic build only: which ck_marg_kernel the last chunked call launched
 extern "C" int lt_diag_chunk_marg_len(void) { return g_last_marg_len; }
+// diagnostic build only: whether the last chunked call launched the specialised phase A
+extern "C" int lt_diag_chunk_ab_spec(void) { return g_last_ab_spec; }
 #endif
 
 namespace lt_impl {
