@@ -496,5 +496,7 @@ const char* lt_version(void);
 #include "lt_posterior.h"
 /* Expected values over the alignments of a label string, likewise. */
 #include "lt_string_expect.h"
+/* Scoring given paths, scattering per-path gradients, edit distance, likewise. */
+#include "lt_paths.h"
 
 #endif /* LT_LATTICE_H_ */

@@ -10,5 +10,6 @@ from last_torch_amd import contexts
 from last_torch_amd import semirings
 from last_torch_amd import weight_fns
 from last_torch_amd.lattices import RecognitionLattice
+from last_torch_amd.risk import edit_distance
 
 __version__ = '0.1.0'

@@ -101,6 +101,9 @@ _SIG = {
     'lt_table_sample_workspace_bytes': [_G, _TP, _I32, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_sample': [_G, _TP, _P, _P, _P, _P, _I32, ctypes.c_uint64, _P, _P, _P,
                         ctypes.c_size_t, _P],
+    'lt_table_path_score': [_G, _TP, _P, _P, _P, _I32, _P, _P, _P],
+    'lt_table_path_scatter': [_G, _TP, _P, _P, _P, _I32, _P, _P, _P],
+    'lt_edit_distance': [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
     'lt_table_expectation_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_expectation': [_G, _TP] + [_P] * 8 + [ctypes.c_size_t, _P],
     'lt_joint_weights_workspace_bytes': [ctypes.c_int64, _I32, _I32,
@@ -130,7 +133,8 @@ _SIG = {
 # alignment), include/lt_sample.h (path sampling), include/lt_expect.h
 # (posterior means of arc values), include/lt_posterior.h (emission posteriors
 # of a label string), include/lt_string_expect.h (expected values over a label
-# string's alignments, the string scatter) and include/lt_lattice.h (everything
+# string's alignments, the string scatter), include/lt_paths.h (scoring given
+# paths, the path scatter, edit distance) and include/lt_lattice.h (everything
 # else)
 EXPORTED_ALIGN = ('lt_table_align_workspace_bytes', 'lt_table_align')
 EXPORTED_SAMPLE = ('lt_table_sample_workspace_bytes', 'lt_table_sample')
@@ -138,9 +142,10 @@ EXPORTED_EXPECT = ('lt_table_expectation_workspace_bytes', 'lt_table_expectation
 EXPORTED_POSTERIOR = ('lt_table_align_posteriors_workspace_bytes', 'lt_table_align_posteriors')
 EXPORTED_ALIGN_EXPECT = ('lt_table_align_expectation_workspace_bytes',
                          'lt_table_align_expectation', 'lt_table_string_scatter')
+EXPORTED_PATHS = ('lt_table_path_score', 'lt_table_path_scatter', 'lt_edit_distance')
 EXPORTED = (tuple(n for n in _SIG
                   if n not in (EXPORTED_ALIGN + EXPORTED_SAMPLE + EXPORTED_EXPECT +
-                               EXPORTED_POSTERIOR + EXPORTED_ALIGN_EXPECT)) +
+                               EXPORTED_POSTERIOR + EXPORTED_ALIGN_EXPECT + EXPORTED_PATHS)) +
             ('lt_last_error', 'lt_version'))
 
 
@@ -811,6 +816,100 @@ def table_sample(graph, W, num_frames, log_z, alpha, num_samples, seed):
                                _ptr(labels), _ptr(weight), _ptr(ws), nbytes.value, _stream()),
          'lt_table_sample')
   return labels, weight
+
+
+def _path_labels(W, labels):
+  B, T = W.shape[:2]
+  if labels.ndim != 3 or labels.shape[0] != B or labels.shape[2] != T:
+    raise ValueError(f'alignment labels {tuple(labels.shape)} do not match [{B}, S, {T}]')
+  if labels.shape[1] < 1:
+    raise ValueError('alignment labels hold no path (S = 0)')
+  return labels.to(device=W.device, dtype=torch.int64).contiguous()
+
+
+def table_path_score_supported(graph, W, num_paths):
+  """Whether lt_table_path_score takes this problem (FrameDependent, T within
+  its LDS rows): a host-only query on an empty batch, no launch. Other errors
+  raise."""
+  pb = _tproblem(graph, W)
+  pb.batch = 0
+  rc = lib().lt_table_path_score(ctypes.byref(graph.g), ctypes.byref(pb), None, None, None,
+                                 int(num_paths), None, None, None)
+  if rc == LT_EUNSUPPORTED:
+    return False
+  _check(rc, 'lt_table_path_score')
+  return True
+
+
+def table_path_score(graph, W, num_frames, labels, want_states=True):
+  """lt_table_path_score: the weights of the given paths (labels int64
+  [B, S, T], lt_table_sample's layout), one launch. Returns (path weights fp32
+  [B, S], states int32 [B, S, T] or None): the state before each live frame of
+  a valid path, -1 elsewhere."""
+  pb = _tproblem(graph, W)
+  labels = _path_labels(W, labels)
+  B, S, T = labels.shape
+  weight = _f32([B, S], W)
+  states = torch.empty([B, S, T], dtype=torch.int32, device=W.device) if want_states else None
+  _check(lib().lt_table_path_score(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W),
+                                   _ptr(num_frames), _ptr(labels), S, _ptr(weight), _ptr(states),
+                                   _stream()), 'lt_table_path_score')
+  return weight, states
+
+
+def table_path_scatter(graph, W, num_frames, labels, states, grad):
+  """lt_table_path_scatter: the dense fp32 dW [B,T,C,V+1] (W's shape) of one
+  scalar grad [B, S] per path, put on the arcs (states, labels) the path takes:
+  one kernel that also writes the zeros, paths that share an arc summed in
+  ascending s."""
+  pb = _tproblem(graph, W)
+  labels = _path_labels(W, labels)
+  B, S, T = labels.shape
+  if tuple(states.shape) != (B, S, T) or tuple(grad.shape) != (B, S):
+    raise ValueError(f'states {tuple(states.shape)} / grad {tuple(grad.shape)} do not match '
+                     f'[{B}, {S}, {T}] / [{B}, {S}]')
+  states = states.to(device=W.device, dtype=torch.int32).contiguous()
+  grad = grad.to(device=W.device, dtype=torch.float32).contiguous()
+  dW = _f32(tuple(W.shape), W)
+  _check(lib().lt_table_path_scatter(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(num_frames),
+                                     _ptr(labels), _ptr(states), S, _ptr(grad), _ptr(dW),
+                                     _stream()), 'lt_table_path_scatter')
+  return dW
+
+
+def edit_distance_supported(max_labels):
+  """Whether lt_edit_distance takes references of this width (U + 1 <= 1024
+  cells): a host-only query on an empty batch, no launch. Other errors raise."""
+  rc = lib().lt_edit_distance(0, 1, 0, int(max_labels), None, None, None, None, None, None, None)
+  if rc == LT_EUNSUPPORTED:
+    return False
+  _check(rc, 'lt_edit_distance')
+  return True
+
+
+def edit_distance(hyp, num_frames, ref, num_labels, want_length=True):
+  """lt_edit_distance: the Levenshtein distance of the tokens (values > 0) of
+  hyp int64 [B, S, T] (the first num_frames[b] positions; None: all T) against
+  those of ref int32 [B, U] (the first num_labels[b]), one launch. Returns
+  (distance int32 [B, S], hypothesis token counts int32 [B, S] or None)."""
+  if not hyp.is_cuda:
+    raise LatticeLibraryError('lattice kernels need the hypotheses on a ROCm device')
+  if hyp.ndim != 3 or ref.ndim != 2 or ref.shape[0] != hyp.shape[0]:
+    raise ValueError(f'hyp {tuple(hyp.shape)} / ref {tuple(ref.shape)} do not match [B, S, T] / '
+                     '[B, U]')
+  B, S, T = hyp.shape
+  U = ref.shape[1]
+  hyp = hyp.to(torch.int64).contiguous()
+  ref = ref.to(device=hyp.device, dtype=torch.int32).contiguous()
+  num_labels = num_labels.to(device=hyp.device, dtype=torch.int32).contiguous()
+  if num_frames is not None:
+    num_frames = num_frames.to(device=hyp.device, dtype=torch.int32).contiguous()
+  dist = torch.empty([B, S], dtype=torch.int32, device=hyp.device)
+  length = torch.empty([B, S], dtype=torch.int32, device=hyp.device) if want_length else None
+  _check(lib().lt_edit_distance(B, S, T, U, _ptr(hyp), _ptr(num_frames), _ptr(ref),
+                                _ptr(num_labels), _ptr(dist), _ptr(length), _stream()),
+         'lt_edit_distance')
+  return dist, length
 
 
 def table_expectation(graph, W, values, num_frames, want_marg=True, want_cov=True):

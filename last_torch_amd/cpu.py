@@ -4,10 +4,11 @@
 the HIP kernels (liblt_lattice.so) when they live on a ROCm device: the
 device of the tensors picks the implementation, as in the reference, and
 there is no fallback from one to the other (a ROCm tensor never runs on the
-host; a missing HIP library raises). The two functions here that also take
-ROCm tensors are align_posteriors and align_expectation, which then run their
-torch ops on that device: RecognitionLattice.align_posteriors and
-align_expectation past their kernels' range.
+host; a missing HIP library raises). The functions here that also take ROCm
+tensors are align_posteriors, align_expectation, path_weights and
+edit_distance, which then run their torch ops on that device:
+RecognitionLattice.align_posteriors, align_expectation and path_weights and
+last_torch_amd.edit_distance past their kernels' range.
 
 One formulation covers both alignment lattices and any context dependency.
 A frame of FrameDependent (K = 0) or FrameLabelDependent(K) is
@@ -43,6 +44,13 @@ MaxTropical's first-argmax rule prefers the blank, then fewer expansions.
   sample        (not in the reference) paths from the posterior exp(w) / Z:
                                       Gumbel-max on Philox4x32-10, walked
                                       backwards over alpha (lt_sample.h)
+  path_weights  (not in the reference) the weight of given paths (lt_paths.h):
+                                      a table walk and a gather, summed from
+                                      the last frame to the first as
+                                      lt_sample.h does; plain autograd
+  edit_distance (not in the reference) Levenshtein distance of the tokens of
+                                      hypotheses against references
+                                      (lt_paths.h), one DP row per token
   expectation   (not in the reference) posterior mean of an arc-additive path
                                       value (lt_expect.h): the arc marginals
                                       by autograd with a graph, so the result
@@ -498,3 +506,88 @@ def sample(W: torch.Tensor, nf: torch.Tensor, context: contexts.ContextDependenc
   labels = torch.where(sampled[:, None, None], labels, torch.zeros_like(labels))
   weight = torch.where(sampled[:, None], weight, neg)
   return labels, weight, log_z
+
+
+# ---------------------------------------------------------------------------
+# Scoring given paths and the edit distance of hypotheses (include/lt_paths.h)
+# ---------------------------------------------------------------------------
+def path_weights(W: torch.Tensor, nf: torch.Tensor, labels: torch.Tensor,
+                 context: contexts.ContextDependency):
+  """(path weights [B, S], states int32 [B, S, T]) of the paths labels
+  [B, S, T] (the true label per frame, 0 = blank) through W [B, T, C, V+1], by
+  the definition of include/lt_paths.h in torch ops: the walk of the
+  next-state table from state 0 (one step per frame, vectorised over
+  utterances and paths), one gather, and the fp32 sum taken from the last
+  frame to the first, the order of `sample`. A live label outside [0, V]
+  gives weight -inf and states -1. Differentiable w.r.t. W by plain autograd;
+  device-agnostic."""
+  if not hasattr(context, 'next_state_table'):
+    raise NotImplementedError(f'{type(context).__name__} has no next-state table')
+  table = context.next_state_table
+  table = torch.as_tensor(table() if callable(table) else table).to(W.device).long()
+  dev = W.device
+  B, T, C, R = W.shape
+  V = R - 1
+  labels = labels.to(dev).long()
+  if labels.ndim != 3 or labels.shape[0] != B or labels.shape[2] != T:
+    raise ValueError(f'alignment labels {tuple(labels.shape)} do not match [{B}, S, {T}]')
+  S = labels.shape[1]
+  nf = nf.to(dev).long().clamp(0, T)
+  live = torch.arange(T, device=dev)[None, None, :] < nf[:, None, None]      # [B, 1, T]
+  inside = (labels >= 0) & (labels <= V)
+  valid = (inside | ~live).all(dim=-1)                                        # [B, S]
+  lex = live & (labels >= 1) & (labels <= V)
+  q = torch.zeros([B, S], dtype=torch.int64, device=dev)
+  states = []
+  for t in range(T):
+    states.append(q)
+    y = labels[:, :, t]
+    q = torch.where(lex[:, :, t], table[q, (y - 1).clamp(0, V - 1)], q)
+  states = torch.stack(states, dim=2) if states else q.new_zeros([B, S, 0])
+  on = live & valid[:, :, None]                                               # [B, S, T]
+  k = states * R + labels.clamp(0, V)
+  w = torch.gather(W.float().reshape(B, T, C * R), 2, k.permute(0, 2, 1)).permute(0, 2, 1)
+  w = torch.where(on, w, torch.zeros_like(w))
+  total = torch.zeros([B, S], dtype=torch.float32, device=dev)
+  for t in range(T - 1, -1, -1):
+    total = total + w[:, :, t]
+  total = torch.where(valid, total, torch.full_like(total, -torch.inf))
+  states = torch.where(on, states, torch.full_like(states, -1)).to(torch.int32)
+  return total, states
+
+
+def edit_distance(hyp: torch.Tensor, nf, ref: torch.Tensor, nl: torch.Tensor):
+  """(distance int32 [B, S], hypothesis token counts int32 [B, S]) by the
+  definition of include/lt_paths.h in torch ops: the tokens (values > 0) of
+  hyp [B, S, T] below nf [B] (None: all T) against those of ref [B, U] below
+  nl [B], unit-cost Levenshtein; nl outside [0, U] gives -1. One DP row
+  update per hypothesis token, vectorised over utterances, hypotheses and
+  reference positions, with the insertion chain as a cumulative minimum.
+  Device-agnostic."""
+  dev = hyp.device
+  hyp = hyp.long()
+  B, S, T = hyp.shape
+  ref = ref.to(dev).long().reshape(B, -1)
+  U = ref.shape[1]
+  nl = nl.to(dev).long()
+  ranged = (nl >= 0) & (nl <= U)
+  nfc = torch.full([B], T, device=dev) if nf is None else nf.to(dev).long().clamp(0, T)
+  hok = (hyp > 0) & (torch.arange(T, device=dev)[None, None, :] < nfc[:, None, None])
+  rok = (ref > 0) & (torch.arange(U, device=dev)[None, :] < nl[:, None])
+  # tokens first, in their order
+  hyp_c = torch.gather(hyp, 2, torch.argsort((~hok).long(), dim=2, stable=True))
+  ref_c = torch.gather(ref, 1, torch.argsort((~rok).long(), dim=1, stable=True))
+  hlen = hok.sum(dim=2)                                                       # [B, S]
+  n = rok.sum(dim=1)                                                          # [B]
+  j = torch.arange(U + 1, device=dev)
+  D = j.expand(B, S, U + 1)
+  big = torch.full([B, S, 1], T + U + 2, device=dev)
+  for i in range(int(hlen.max()) if hlen.numel() else 0):
+    h = hyp_c[:, :, i]
+    sub = D[:, :, :-1] + (ref_c[:, None, :] != h[:, :, None]).long()
+    tmp = torch.minimum(D + 1, torch.cat([big, sub], dim=2))
+    new = j + torch.cummin(tmp - j, dim=2).values
+    D = torch.where((i < hlen)[:, :, None], new, D)
+  dist = torch.gather(D, 2, n[:, None, None].expand(B, S, 1))[..., 0]
+  dist = torch.where(ranged[:, None], dist, torch.full_like(dist, -1))
+  return dist.to(torch.int32), hlen.to(torch.int32)

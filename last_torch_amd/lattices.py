@@ -28,6 +28,13 @@ weights once through the ``WeightFn`` plugin as a contiguous
                      its range cpu.align_expectation on the device
   sample          -> lt_den_forward / lt_table_forward (Log) + lt_table_sample
                      (paths from the posterior; not in the reference)
+  path_weights    -> lt_table_path_score (the weight of given alignment paths;
+                     not in the reference) + lt_table_path_scatter in the
+                     backward; past its range cpu.path_weights on the device
+  sampled_risk    -> sample's calls + lt_table_path_score + lt_edit_distance
+                     (minimum-risk training from sampled paths; not in the
+                     reference); backward: lt_table_path_scatter, and
+                     lt_den_backward / lt_table_den_backward only at S = 1
   expectation     -> lt_table_expectation (posterior mean of arc values with
                      its gradients; not in the reference), also behind
                      entropy(differentiable=True)
@@ -53,6 +60,7 @@ from last_torch_amd import _native_cpu
 from last_torch_amd import alignments
 from last_torch_amd import cpu
 from last_torch_amd import contexts
+from last_torch_amd import risk as risk_lib
 from last_torch_amd import semirings
 from last_torch_amd import weight_fns
 
@@ -314,6 +322,28 @@ class _AlignExpectFn(torch.autograd.Function):
     if need_b:
       db = (g_e * blank_occ).to(bv.dtype)
     return dW, dl, db, None, None, None, None
+
+
+class _PathScoreFn(torch.autograd.Function):
+  """The weights of given paths (include/lt_paths.h): the forward is ONE
+  lt_table_path_score call that keeps the states it walked; the backward is
+  ONE lt_table_path_scatter call that puts each path's incoming gradient on
+  its arcs. A second backward (retain_graph) reuses the saved states."""
+
+  @staticmethod
+  def forward(ctx, W, nf, labels, graph):
+    need = ctx.needs_input_grad[0]
+    weight, states = _native.table_path_score(graph, W, nf, labels, want_states=need)
+    ctx.graph = graph
+    if need:
+      ctx.save_for_backward(W, nf, labels, states)
+    return weight
+
+  @staticmethod
+  def backward(ctx, g):
+    W, nf, labels, states = ctx.saved_tensors
+    dW = _native.table_path_scatter(ctx.graph, W, nf, labels, states, g.float())
+    return dW.to(W.dtype), None, None, None
 
 
 class _TableNumFn(torch.autograd.Function):
@@ -791,6 +821,126 @@ class RecognitionLattice(nn.Module, Generic[T]):
     return (self._home(labels.reshape(*batch_dims, S, T), frames),
             self._home(weights.reshape(*batch_dims, S), frames),
             self._home(log_z.reshape(batch_dims), frames))
+
+  def _path_weights(self, W, nf, paths):
+    """path weights [B, S] of paths [B, S, T] over prepared W / nf,
+    differentiable w.r.t. W."""
+    if W.device.type == 'cuda':
+      graph = self._graph(W.device)
+      if _native.table_path_score_supported(graph, W, paths.shape[1]):
+        return _PathScoreFn.apply(W, nf, paths.contiguous(), graph)
+      return cpu.path_weights(W, nf, paths, contexts.NextStateTable(graph.table))[0]
+    return cpu.path_weights(W, nf, paths, self.context)[0]
+
+  def path_weights(self, frames: torch.Tensor, num_frames: torch.Tensor,
+                   alignment_labels: torch.Tensor, cache: Optional[T] = None) -> torch.Tensor:
+    """The weights [batch..., S] of given alignment paths (not in the
+    reference): alignment_labels [batch..., S, T] holds the true label y of
+    the arc each path takes on each frame (0 = blank), the layout `sample`
+    returns -- and what `align` and shortest_path(label_convention='true')
+    return on FrameDependent, with an S axis added. The definition is
+    include/lt_paths.h: a path walks the context's next-state table from the
+    start state, and its weight is the fp32 sum of its arc weights added from
+    the last live frame to the first, so the paths `sample` returned score to
+    its path_weights bit for bit. Labels on padding frames are ignored; a
+    live label outside [0, V] gives weight -inf and no gradient; num_frames
+    = 0 gives 0.
+
+    Differentiable w.r.t. the weight function: the gradient of a path's
+    weight is the indicator of its arcs. FrameDependent with any context that
+    has a next-state table; FrameLabelDependent raises NotImplementedError.
+    """
+    if not isinstance(self.alignment, alignments.FrameDependent):
+      raise NotImplementedError('path_weights implements FrameDependent alignments, got '
+                                f'{type(self.alignment).__name__}')
+    W, nf, batch_dims, B, _, _, _ = self._prepare(cache, frames, num_frames)
+    paths = torch.as_tensor(alignment_labels)
+    Tn = W.shape[1]
+    if (paths.ndim != len(batch_dims) + 2 or tuple(paths.shape[:-2]) != batch_dims or
+        paths.shape[-1] != Tn):
+      raise ValueError(f'alignment_labels should be [batch..., S, {Tn}] with batch dims '
+                       f'{batch_dims}, got {tuple(paths.shape)}')
+    S = paths.shape[-2]
+    if S < 1:
+      raise ValueError('alignment_labels holds no path (S = 0)')
+    paths = paths.to(device=W.device, dtype=torch.int64).reshape(B, S, Tn)
+    weights = self._path_weights(W, nf, paths)
+    return self._home(weights.reshape(*batch_dims, S), frames)
+
+  def sampled_risk(self, frames: torch.Tensor, num_frames: torch.Tensor, labels: torch.Tensor,
+                   num_labels: torch.Tensor, num_samples: int, seed: int,
+                   cost_fn: Optional[Callable[[torch.Tensor, torch.Tensor], torch.Tensor]] = None,
+                   cache: Optional[T] = None):
+    """Minimum-risk (expected-cost) training from sampled paths (not in the
+    reference): the risk R = sum_pi p(pi) c(pi) of a path cost c under the
+    lattice posterior p(pi) = exp(w(pi)) / Z, estimated from num_samples paths
+    drawn exactly as `sample` draws them (same seed contract).
+
+    Returns (risk [batch...], costs [batch..., S], alignment_labels
+    [batch..., S, T]). The default cost is the edit distance
+    (last_torch_amd.edit_distance) of each path's labels to labels /
+    num_labels, as float32; cost_fn(alignment_labels, num_frames) ->
+    [batch..., S] replaces it. risk = costs.mean(-1) in value. An unsampled
+    utterance (log_z not finite) has risk 0, costs 0 and a zero gradient.
+
+    Gradient (into the weight function only; none flows into costs or
+    labels). dR/dw_a = Cov_p(c, 1[a in pi]):
+      * S >= 2: the leave-one-out score-function estimator
+        1/(S-1) sum_s (c_s - mean c) 1[a in pi_s], the unbiased sample
+        covariance, as sum_s adv_s * path_weight_s with adv detached. The
+        advantages sum to zero, so the log Z term cancels exactly and no
+        marginal pass runs: the backward is one scatter of S*T scalars.
+      * S = 1 (no baseline): c * (path_weight - log_z), whose gradient
+        c * (1[a in pi] - marginal_a) runs the Log backward of `_forward`.
+    One arc_weights call. FrameDependent with any context that has a
+    next-state table; FrameLabelDependent raises NotImplementedError.
+    """
+    if not isinstance(self.alignment, alignments.FrameDependent):
+      raise NotImplementedError('sampled_risk implements FrameDependent alignments, got '
+                                f'{type(self.alignment).__name__}')
+    S = int(num_samples)
+    if S < 1:
+      raise ValueError(f'num_samples should be >= 1, but got {num_samples}')
+    W, nf, batch_dims, B, V, n, _ = self._prepare(cache, frames, num_frames)
+    Tn = W.shape[1]
+    want_grad = torch.is_grad_enabled() and W.requires_grad
+    # log Z and alpha: in the graph only where the estimator needs d log Z
+    with torch.set_grad_enabled(want_grad and S == 1):
+      if W.device.type == 'cpu':
+        log_z, alpha = cpu.den_forward(W, nf, self.context, self.alignment, semirings.Log)
+      elif self._table_path():
+        log_z, alpha = _TableDenFn.apply(W, nf, self._graph(W.device), _native.SEMIRING_LOG)
+      else:
+        log_z, alpha = _DenFn.apply(W, nf, V, n, _native.SEMIRING_LOG, None)
+    with torch.no_grad():
+      if W.device.type == 'cpu':
+        paths = cpu.sample(W.detach(), nf, self.context, S, seed, log_z=log_z.detach(),
+                           alpha=alpha.detach())[0]
+      else:
+        paths = _native.table_sample(self._graph(W.device), W.detach(), nf, log_z.detach(),
+                                     alpha.detach(), S, seed)[0]
+      shaped = paths.reshape(*batch_dims, S, Tn)
+      if cost_fn is None:
+        costs = risk_lib.edit_distance(shaped, nf.reshape(batch_dims), labels, num_labels)
+      else:
+        costs = cost_fn(self._home(shaped, frames), num_frames)
+      costs = torch.as_tensor(costs).detach().to(device=W.device, dtype=torch.float32)
+      if tuple(costs.shape) != (*batch_dims, S):
+        raise ValueError(f'costs should be {(*batch_dims, S)}, got {tuple(costs.shape)}')
+      sampled = torch.isfinite(log_z.detach())[:, None]                     # [B, 1]
+      costs = torch.where(sampled, costs.reshape(B, S), torch.zeros([], device=W.device))
+      risk = costs.mean(dim=-1)
+      adv = costs if S == 1 else (costs - risk[:, None]) / (S - 1)
+    if want_grad:
+      zero = torch.zeros([], device=W.device)
+      score = torch.where(sampled, self._path_weights(W, nf, paths), zero)
+      if S == 1:
+        score = score - torch.where(sampled, log_z.float()[:, None], zero)
+      surrogate = (adv * score).sum(dim=-1)
+      risk = risk + (surrogate - surrogate.detach())
+    return (self._home(risk.reshape(batch_dims), frames),
+            self._home(costs.reshape(*batch_dims, S), frames),
+            self._home(shaped, frames))
 
   @staticmethod
   def _align_dense(graph, W, nf, lab, nl):
