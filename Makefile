@@ -14,7 +14,7 @@ lg_of = $(subst M1,-1,$(word 1,$(subst _, ,$(1))))
 lgn_of = $(word 1,$(subst _, ,$(1)))
 p_of = $(word 2,$(subst _, ,$(1)))
 LIB := last_torch_amd/liblt_lattice.so
-DEPS := $(CSRC)/lt_kernels.h $(CSRC)/lt_table_common.h $(CSRC)/lt_joint.h include/lt_lattice.h include/lt_align.h include/lt_sample.h include/lt_expect.h include/lt_posterior.h include/lt_string_expect.h include/lt_paths.h
+DEPS := $(CSRC)/lt_kernels.h $(CSRC)/lt_table_common.h $(CSRC)/lt_joint.h include/lt_lattice.h include/lt_align.h include/lt_sample.h include/lt_expect.h include/lt_posterior.h include/lt_string_expect.h include/lt_paths.h include/lt_beam.h
 
 CPULIB := last_torch_amd/liblt_lattice_cpu.so
 CXX ?= g++
@@ -58,6 +58,10 @@ $(OBJ)/lt_sample.o: $(CSRC)/lt_sample.hip $(DEPS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
+$(OBJ)/lt_beam.o: $(CSRC)/lt_beam.hip $(DEPS)
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+
 $(OBJ)/lt_paths.o: $(CSRC)/lt_paths.hip $(DEPS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
@@ -90,7 +94,7 @@ $(OBJ)/lt_joint.o: $(CSRC)/lt_joint.hip $(DEPS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-$(LIB): $(OBJ)/lt_lattice.o $(OBJ)/lt_pipe.o $(OBJ)/lt_chunk.o $(OBJ)/lt_table.o $(OBJ)/lt_align.o $(OBJ)/lt_align_post.o $(OBJ)/lt_align_expect.o $(OBJ)/lt_sample.o $(OBJ)/lt_paths.o $(OBJ)/lt_edit.o $(OBJ)/lt_expect.o $(OBJ)/lt_producer.o $(OBJ)/lt_joint.o $(OBJ)/lt_vit.o $(OBJ)/lt_tri.o $(INST_OBJS)
+$(LIB): $(OBJ)/lt_lattice.o $(OBJ)/lt_pipe.o $(OBJ)/lt_chunk.o $(OBJ)/lt_table.o $(OBJ)/lt_align.o $(OBJ)/lt_align_post.o $(OBJ)/lt_align_expect.o $(OBJ)/lt_sample.o $(OBJ)/lt_beam.o $(OBJ)/lt_paths.o $(OBJ)/lt_edit.o $(OBJ)/lt_expect.o $(OBJ)/lt_producer.o $(OBJ)/lt_joint.o $(OBJ)/lt_vit.o $(OBJ)/lt_tri.o $(INST_OBJS)
 	$(HIPCC) -shared --offload-arch=$(ARCH) -o $@ $^
 
 oracle:
@@ -123,7 +127,7 @@ $(STAMP_OBJ)/lt_tri4.o: $(CSRC)/lt_tri4.hip $(DEPS)
 $(STAMP_OBJ)/lt_tri.o: $(CSRC)/lt_tri.hip $(DEPS)
 	@mkdir -p $(STAMP_OBJ)
 	$(HIPCC) $(HIPFLAGS) -DLT_STAMPS -DLT_DIAG -c -o $@ $<
-stamps: $(STAMP_OBJ)/lt_lattice.o $(STAMP_OBJ)/lt_pipe.o $(OBJ)/lt_chunk.o $(OBJ)/lt_table.o $(OBJ)/lt_align.o $(OBJ)/lt_align_post.o $(OBJ)/lt_align_expect.o $(OBJ)/lt_sample.o $(OBJ)/lt_paths.o $(OBJ)/lt_edit.o $(OBJ)/lt_expect.o $(OBJ)/lt_producer.o $(STAMP_OBJ)/lt_joint.o $(OBJ)/lt_vit.o $(STAMP_OBJ)/lt_tri.o $(STAMP_OBJ)/lt_tri4.o $(foreach v,$(VARIANTS),$(STAMP_OBJ)/lt_inst_$(v).o)
+stamps: $(STAMP_OBJ)/lt_lattice.o $(STAMP_OBJ)/lt_pipe.o $(OBJ)/lt_chunk.o $(OBJ)/lt_table.o $(OBJ)/lt_align.o $(OBJ)/lt_align_post.o $(OBJ)/lt_align_expect.o $(OBJ)/lt_sample.o $(OBJ)/lt_beam.o $(OBJ)/lt_paths.o $(OBJ)/lt_edit.o $(OBJ)/lt_expect.o $(OBJ)/lt_producer.o $(STAMP_OBJ)/lt_joint.o $(OBJ)/lt_vit.o $(STAMP_OBJ)/lt_tri.o $(STAMP_OBJ)/lt_tri4.o $(foreach v,$(VARIANTS),$(STAMP_OBJ)/lt_inst_$(v).o)
 	$(HIPCC) -shared --offload-arch=$(ARCH) -o $(STAMP_OBJ)/liblt_lattice_stamps.so $^
 .PHONY: stamps
 
@@ -136,7 +140,7 @@ $(DIAG_OBJ)/lt_inst_%.o: $(CSRC)/lt_inst.hip $(DEPS)
 $(DIAG_OBJ)/%.o: $(CSRC)/%.hip $(DEPS)
 	@mkdir -p $(DIAG_OBJ)
 	$(HIPCC) $(HIPFLAGS) -DLT_DIAG -c -o $@ $<
-diag: $(DIAG_OBJ)/lt_lattice.o $(DIAG_OBJ)/lt_pipe.o $(DIAG_OBJ)/lt_chunk.o $(DIAG_OBJ)/lt_table.o $(DIAG_OBJ)/lt_align.o $(DIAG_OBJ)/lt_align_post.o $(DIAG_OBJ)/lt_align_expect.o $(DIAG_OBJ)/lt_sample.o $(DIAG_OBJ)/lt_paths.o $(DIAG_OBJ)/lt_edit.o $(DIAG_OBJ)/lt_expect.o $(DIAG_OBJ)/lt_producer.o $(DIAG_OBJ)/lt_joint.o $(DIAG_OBJ)/lt_vit.o $(DIAG_OBJ)/lt_tri.o $(DIAG_OBJ)/lt_tri4.o $(foreach v,$(VARIANTS),$(DIAG_OBJ)/lt_inst_$(v).o)
+diag: $(DIAG_OBJ)/lt_lattice.o $(DIAG_OBJ)/lt_pipe.o $(DIAG_OBJ)/lt_chunk.o $(DIAG_OBJ)/lt_table.o $(DIAG_OBJ)/lt_align.o $(DIAG_OBJ)/lt_align_post.o $(DIAG_OBJ)/lt_align_expect.o $(DIAG_OBJ)/lt_sample.o $(DIAG_OBJ)/lt_beam.o $(DIAG_OBJ)/lt_paths.o $(DIAG_OBJ)/lt_edit.o $(DIAG_OBJ)/lt_expect.o $(DIAG_OBJ)/lt_producer.o $(DIAG_OBJ)/lt_joint.o $(DIAG_OBJ)/lt_vit.o $(DIAG_OBJ)/lt_tri.o $(DIAG_OBJ)/lt_tri4.o $(foreach v,$(VARIANTS),$(DIAG_OBJ)/lt_inst_$(v).o)
 	$(HIPCC) -shared --offload-arch=$(ARCH) -o $(DIAG_OBJ)/liblt_lattice_diag.so $^
 .PHONY: diag
 

@@ -498,5 +498,7 @@ const char* lt_version(void);
 #include "lt_string_expect.h"
 /* Scoring given paths, scattering per-path gradients, edit distance, likewise. */
 #include "lt_paths.h"
+/* Prefix beam search: the N best label sequences, likewise. */
+#include "lt_beam.h"
 
 #endif /* LT_LATTICE_H_ */

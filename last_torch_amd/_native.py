@@ -101,6 +101,9 @@ _SIG = {
     'lt_table_sample_workspace_bytes': [_G, _TP, _I32, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_sample': [_G, _TP, _P, _P, _P, _P, _I32, ctypes.c_uint64, _P, _P, _P,
                         ctypes.c_size_t, _P],
+    'lt_table_beam_search_workspace_bytes': [_G, _TP, _I32, ctypes.POINTER(ctypes.c_size_t)],
+    'lt_table_beam_search': [_G, _TP, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P,
+                             ctypes.c_size_t, _P],
     'lt_table_path_score': [_G, _TP, _P, _P, _P, _I32, _P, _P, _P],
     'lt_table_path_scatter': [_G, _TP, _P, _P, _P, _I32, _P, _P, _P],
     'lt_edit_distance': [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
@@ -134,8 +137,8 @@ _SIG = {
 # (posterior means of arc values), include/lt_posterior.h (emission posteriors
 # of a label string), include/lt_string_expect.h (expected values over a label
 # string's alignments, the string scatter), include/lt_paths.h (scoring given
-# paths, the path scatter, edit distance) and include/lt_lattice.h (everything
-# else)
+# paths, the path scatter, edit distance), include/lt_beam.h (prefix beam
+# search) and include/lt_lattice.h (everything else)
 EXPORTED_ALIGN = ('lt_table_align_workspace_bytes', 'lt_table_align')
 EXPORTED_SAMPLE = ('lt_table_sample_workspace_bytes', 'lt_table_sample')
 EXPORTED_EXPECT = ('lt_table_expectation_workspace_bytes', 'lt_table_expectation')
@@ -143,9 +146,11 @@ EXPORTED_POSTERIOR = ('lt_table_align_posteriors_workspace_bytes', 'lt_table_ali
 EXPORTED_ALIGN_EXPECT = ('lt_table_align_expectation_workspace_bytes',
                          'lt_table_align_expectation', 'lt_table_string_scatter')
 EXPORTED_PATHS = ('lt_table_path_score', 'lt_table_path_scatter', 'lt_edit_distance')
+EXPORTED_BEAM = ('lt_table_beam_search_workspace_bytes', 'lt_table_beam_search')
 EXPORTED = (tuple(n for n in _SIG
                   if n not in (EXPORTED_ALIGN + EXPORTED_SAMPLE + EXPORTED_EXPECT +
-                               EXPORTED_POSTERIOR + EXPORTED_ALIGN_EXPECT + EXPORTED_PATHS)) +
+                               EXPORTED_POSTERIOR + EXPORTED_ALIGN_EXPECT + EXPORTED_PATHS +
+                               EXPORTED_BEAM)) +
             ('lt_last_error', 'lt_version'))
 
 
@@ -816,6 +821,51 @@ def table_sample(graph, W, num_frames, log_z, alpha, num_samples, seed):
                                _ptr(labels), _ptr(weight), _ptr(ws), nbytes.value, _stream()),
          'lt_table_sample')
   return labels, weight
+
+
+def table_beam_search_supported(graph, W, beam_size):
+  """Whether lt_table_beam_search takes this problem (FrameDependent,
+  beam_size <= 64, V <= 1023): a host-only query, no launch. Other errors
+  raise."""
+  pb = _tproblem(graph, W)
+  nbytes = ctypes.c_size_t(0)
+  rc = lib().lt_table_beam_search_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
+                                                  int(beam_size), ctypes.byref(nbytes))
+  if rc == LT_EUNSUPPORTED:
+    return False
+  _check(rc, 'lt_table_beam_search_workspace_bytes')
+  return True
+
+
+def table_beam_search(graph, W, num_frames, beam_size, semiring, want_trace=False):
+  """lt_table_beam_search: the beam_size best label sequences per utterance,
+  one launch. Returns (labels int64 [B, K, T], num_labels int32 [B, K], scores
+  fp32 [B, K]) and, with want_trace, (trace int32 [B, T, K], step_score fp32
+  [B, T, K]); raises LatticeLibraryError (LT_EUNSUPPORTED) past the kernel's
+  range."""
+  pb = _tproblem(graph, W)
+  B, T = W.shape[:2]
+  K = int(beam_size)
+  nbytes = ctypes.c_size_t(0)
+  _check(lib().lt_table_beam_search_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb), K,
+                                                    ctypes.byref(nbytes)),
+         'lt_table_beam_search_workspace_bytes')
+  labels = torch.empty([B, K, T], dtype=torch.int64, device=W.device)
+  num_labels = torch.empty([B, K], dtype=torch.int32, device=W.device)
+  scores = _f32([B, K], W)
+  trace = step = ws = None
+  if want_trace:
+    trace = torch.empty([B, T, K], dtype=torch.int32, device=W.device)
+    step = _f32([B, T, K], W)
+  elif nbytes.value:  # the backpointers of a call without a trace
+    ws = torch.empty([nbytes.value], dtype=torch.uint8, device=W.device)
+  _check(lib().lt_table_beam_search(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W),
+                                    _ptr(num_frames), K, semiring, _ptr(labels),
+                                    _ptr(num_labels), _ptr(scores), _ptr(trace), _ptr(step),
+                                    _ptr(ws), nbytes.value if ws is not None else 0, _stream()),
+         'lt_table_beam_search')
+  out = (labels, num_labels, scores)
+  return out + (trace, step) if want_trace else out
 
 
 def _path_labels(W, labels):

@@ -5,10 +5,10 @@ the HIP kernels (liblt_lattice.so) when they live on a ROCm device: the
 device of the tensors picks the implementation, as in the reference, and
 there is no fallback from one to the other (a ROCm tensor never runs on the
 host; a missing HIP library raises). The functions here that also take ROCm
-tensors are align_posteriors, align_expectation, path_weights and
-edit_distance, which then run their torch ops on that device:
-RecognitionLattice.align_posteriors, align_expectation and path_weights and
-last_torch_amd.edit_distance past their kernels' range.
+tensors are align_posteriors, align_expectation, path_weights, beam_search
+and edit_distance, which then run their torch ops on that device:
+RecognitionLattice.align_posteriors, align_expectation, path_weights and
+beam_search and last_torch_amd.edit_distance past their kernels' range.
 
 One formulation covers both alignment lattices and any context dependency.
 A frame of FrameDependent (K = 0) or FrameLabelDependent(K) is
@@ -51,6 +51,9 @@ MaxTropical's first-argmax rule prefers the blank, then fewer expansions.
   edit_distance (not in the reference) Levenshtein distance of the tokens of
                                       hypotheses against references
                                       (lt_paths.h), one DP row per token
+  beam_search   (not in the reference) the N best label sequences by prefix
+                                      beam search (lt_beam.h): one gather,
+                                      merge and stable sort per frame
   expectation   (not in the reference) posterior mean of an arc-additive path
                                       value (lt_expect.h): the arc marginals
                                       by autograd with a graph, so the result
@@ -591,3 +594,125 @@ def edit_distance(hyp: torch.Tensor, nf, ref: torch.Tensor, nl: torch.Tensor):
   dist = torch.gather(D, 2, n[:, None, None].expand(B, S, 1))[..., 0]
   dist = torch.where(ranged[:, None], dist, torch.full_like(dist, -1))
   return dist.to(torch.int32), hlen.to(torch.int32)
+
+
+# ---------------------------------------------------------------------------
+# Prefix beam search: the N best label sequences (include/lt_beam.h)
+# ---------------------------------------------------------------------------
+_M64 = (1 << 64) - 1
+
+
+def _i64(x: int) -> int:
+  """The int64 that holds the bits of the unsigned 64-bit x."""
+  x &= _M64
+  return x - (1 << 64) if x >> 63 else x
+
+
+def _lsr(z: torch.Tensor, k: int) -> torch.Tensor:
+  """Logical shift right of int64 bit patterns."""
+  return (z >> k) & ((1 << (64 - k)) - 1)
+
+
+def prefix_hash(h: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+  """mix(h, y) of include/lt_beam.h on int64 tensors holding unsigned 64-bit
+  patterns (int64 products wrap, shifts are made logical)."""
+  z = h ^ (y * _i64(0x9E3779B97F4A7C15))
+  z = (z ^ _lsr(z, 30)) * _i64(0xBF58476D1CE4E5B9)
+  z = (z ^ _lsr(z, 27)) * _i64(0x94D049BB133111EB)
+  return z ^ _lsr(z, 31)
+
+
+def beam_search(W: torch.Tensor, nf: torch.Tensor, context: contexts.ContextDependency,
+                beam_size: int, semiring, want_trace: bool = False):
+  """The beam_size best label sequences per utterance of the denominator
+  lattice x FrameDependent, by the definition of include/lt_beam.h in torch
+  ops, fp32: one step per frame, vectorised over utterances, slots and labels
+  (candidates, the merge of a prefix with its parent's extension, a stable
+  descending sort for the selection), then the backtrace of the trace.
+  Device-agnostic. Returns (labels int64 [B, K, T], num_labels int64 [B, K],
+  scores fp32 [B, K]) and, with want_trace, (trace int32 [B, T, K], step_score
+  fp32 [B, T, K])."""
+  if not hasattr(context, 'next_state_table'):
+    raise NotImplementedError(f'{type(context).__name__} has no next-state table')
+  name = getattr(semiring, 'name', None)
+  if name not in ('Log', 'MaxTropical'):
+    raise NotImplementedError(f'beam_search supports Log and MaxTropical, got {semiring!r}')
+  K = int(beam_size)
+  if K < 1:
+    raise ValueError(f'beam_size should be >= 1, but got {beam_size}')
+  table = context.next_state_table
+  table = torch.as_tensor(table() if callable(table) else table).to(W.device).long()
+  W = W.float()
+  dev = W.device
+  B, T, C, R = W.shape
+  nf = nf.to(dev).long().clamp(0, T)
+  neg = torch.tensor(-torch.inf, device=dev)
+  s = torch.full([B, K], -torch.inf, device=dev)
+  s[:, 0] = 0.
+  c = torch.zeros([B, K], dtype=torch.int64, device=dev)
+  n, h, ph, y = (torch.zeros_like(c) for _ in range(4))
+  trace = torch.full([B, T, K], -1, dtype=torch.int32, device=dev)
+  step = torch.full([B, T, K], -torch.inf, device=dev)
+  last = int(nf.max()) if B else 0
+  for t in range(last):
+    rows = torch.gather(W[:, t], 1, c[:, :, None].expand(B, K, R))             # [B, K, R]
+    cand = s[:, :, None] + rows
+    cand = torch.where(torch.isnan(cand), neg, cand)
+    alive = s > -torch.inf
+    # merge: slot i's parent j, whose extension by y_i is slot i's prefix
+    match = (alive[:, :, None] & alive[:, None, :] & (n[:, :, None] >= 1) &
+             (h[:, None, :] == ph[:, :, None]) & (n[:, None, :] == n[:, :, None] - 1))
+    has = match.any(dim=2)
+    j = match.to(torch.int8).argmax(dim=2)                                    # the lowest
+    flat = cand.reshape(B, K * R)
+    at = j * R + y
+    ext = torch.gather(flat, 1, at)
+    blank = cand[:, :, 0]
+    if name == 'Log':
+      both = torch.logaddexp(blank, ext)
+      both = torch.where((blank == -torch.inf) & (ext == -torch.inf), neg, both)
+    else:
+      both = torch.where(blank >= ext, blank, ext)
+    both = torch.where(torch.isnan(both), neg, both)
+    gone = torch.zeros([B, K * R + 1], dtype=torch.bool, device=dev)
+    gone.scatter_(1, torch.where(has, at, torch.full_like(at, K * R)), True)
+    flat = torch.where(gone[:, :K * R], neg, flat).reshape(B, K, R).clone()
+    flat[:, :, 0] = torch.where(has, both, blank)
+    # select: larger score first, equal scores to the smaller k (stable sort)
+    val, k = torch.sort(flat.reshape(B, K * R), dim=1, descending=True, stable=True)
+    val, k = val[:, :K], k[:, :K]
+    kept = val > -torch.inf
+    src, yw = k // R, k % R
+    g = lambda x: torch.gather(x, 1, src)
+    ext_sel = yw > 0
+    hs = g(h)
+    new = dict(
+        s=torch.where(kept, val, neg),
+        c=torch.where(ext_sel, table[g(c), (yw - 1).clamp(min=0)], g(c)),
+        n=g(n) + ext_sel.long(),
+        h=torch.where(ext_sel, prefix_hash(hs, yw), hs),
+        ph=torch.where(ext_sel, hs, g(ph)),
+        y=torch.where(ext_sel, yw, g(y)))
+    zero = torch.zeros_like(c)
+    for key in ('c', 'n', 'h', 'ph', 'y'):
+      new[key] = torch.where(kept, new[key], zero)
+    live = (t < nf)[:, None]
+    s, c, n = torch.where(live, new['s'], s), torch.where(live, new['c'], c), torch.where(live, new['n'], n)
+    h, ph, y = torch.where(live, new['h'], h), torch.where(live, new['ph'], ph), torch.where(live, new['y'], y)
+    trace[:, t] = torch.where(live & kept, (src << 16) | yw, torch.full_like(src, -1)).to(torch.int32)
+    step[:, t] = torch.where(live & kept, val, neg)
+  # backtrace: each final slot's labels, back to front
+  labels = torch.zeros([B, K, T + 1], dtype=torch.int64, device=dev)   # column T: scratch
+  cur = torch.arange(K, device=dev).expand(B, K)
+  pos = n.clone()
+  for t in range(last - 1, -1, -1):
+    e = torch.gather(trace[:, t].long(), 1, cur)
+    on = (t < nf)[:, None] & (s > -torch.inf) & (e >= 0)
+    yy = e & 0xffff
+    put = on & (yy > 0) & (pos > 0)
+    pos = pos - put.long()
+    labels.scatter_(2, torch.where(put, pos, torch.full_like(pos, T))[:, :, None],
+                    torch.where(put, yy, torch.zeros_like(yy))[:, :, None])
+    cur = torch.where(on, e >> 16, cur)
+  out = (labels[:, :, :T].contiguous(), n, s)
+  return out + (trace, step) if want_trace else out

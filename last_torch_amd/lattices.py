@@ -28,6 +28,9 @@ weights once through the ``WeightFn`` plugin as a contiguous
                      its range cpu.align_expectation on the device
   sample          -> lt_den_forward / lt_table_forward (Log) + lt_table_sample
                      (paths from the posterior; not in the reference)
+  beam_search     -> lt_table_beam_search (the N best label sequences by
+                     prefix beam search; not in the reference); past its range
+                     cpu.beam_search on the device
   path_weights    -> lt_table_path_score (the weight of given alignment paths;
                      not in the reference) + lt_table_path_scatter in the
                      backward; past its range cpu.path_weights on the device
@@ -821,6 +824,61 @@ class RecognitionLattice(nn.Module, Generic[T]):
     return (self._home(labels.reshape(*batch_dims, S, T), frames),
             self._home(weights.reshape(*batch_dims, S), frames),
             self._home(log_z.reshape(batch_dims), frames))
+
+  def beam_search(self, frames: torch.Tensor, num_frames: torch.Tensor, beam_size: int,
+                  semiring=semirings.Log, cache: Optional[T] = None):
+    """The beam_size best label sequences with their scores (not in the
+    reference): frame-synchronous beam search over label prefixes, the
+    definition in include/lt_beam.h. A hypothesis is a label prefix; on each
+    frame it stays (the blank arc) or grows by one label, a prefix reached
+    both ways -- by staying, and as its parent's extension -- is one
+    hypothesis whose two scores are (+)-summed, and the beam_size best
+    candidates (larger score first, ties to the lower slot, then the lower
+    label) make the next beam. With semirings.Log a score is the log of the
+    summed weight of the sequence's alignments that the beam kept: at most
+    _string_forward of the sequence, equal to it when nothing was pruned.
+    With semirings.MaxTropical it is the best kept alignment's weight.
+    Neither is normalised: subtract _forward's log_z for a log-probability.
+    shortest_path returns the best alignment; this returns the best label
+    sequences, which need not contain that alignment's.
+
+    Returns (labels [batch..., K, T] int64, num_labels [batch..., K] int64,
+    scores [batch..., K] fp32), best first: a sequence's labels at the front
+    of its row, 0 after them; a slot the search could not fill (fewer than K
+    candidates of finite score) holds all 0 / 0 / -inf; num_frames = 0 gives
+    the empty sequence with score 0. No gradient flows through any of them.
+    `labels` with `num_frames` goes straight into last_torch_amd.edit_distance
+    as hypotheses: the zeros read as blanks. FrameDependent with any context
+    that has a next-state table; FrameLabelDependent raises
+    NotImplementedError. ROCm tensors run lt_table_beam_search (one launch);
+    past its range (beam_size > 64, V > 1023) and on the host, the same
+    definition in torch ops (cpu.beam_search).
+    """
+    if not isinstance(self.alignment, alignments.FrameDependent):
+      raise NotImplementedError('beam_search implements FrameDependent alignments, got '
+                                f'{type(self.alignment).__name__}')
+    K = int(beam_size)
+    if K < 1:
+      raise ValueError(f'beam_size should be >= 1, but got {beam_size}')
+    if getattr(semiring, 'name', None) not in ('Log', 'MaxTropical'):
+      raise NotImplementedError(f'beam_search supports Log and MaxTropical, got {semiring!r}')
+    W, nf, batch_dims, B, _, _, _ = self._prepare(cache, frames, num_frames)
+    with torch.no_grad():
+      W = W.detach()
+      if W.device.type == 'cpu':
+        labels, num_labels, scores = cpu.beam_search(W, nf, self.context, K, semiring)
+      else:
+        graph = self._graph(W.device)
+        if _native.table_beam_search_supported(graph, W, K):
+          labels, num_labels, scores = _native.table_beam_search(graph, W, nf, K,
+                                                                 _semiring_id(semiring))
+        else:
+          labels, num_labels, scores = cpu.beam_search(
+              W, nf, contexts.NextStateTable(graph.table), K, semiring)
+    Tn = W.shape[1]
+    return (self._home(labels.reshape(*batch_dims, K, Tn), frames),
+            self._home(num_labels.long().reshape(*batch_dims, K), frames),
+            self._home(scores.reshape(*batch_dims, K), frames))
 
   def _path_weights(self, W, nf, paths):
     """path weights [B, S] of paths [B, S, T] over prepared W / nf,
