@@ -14,7 +14,7 @@ lg_of = $(subst M1,-1,$(word 1,$(subst _, ,$(1))))
 lgn_of = $(word 1,$(subst _, ,$(1)))
 p_of = $(word 2,$(subst _, ,$(1)))
 LIB := last_torch_amd/liblt_lattice.so
-DEPS := $(CSRC)/lt_kernels.h $(CSRC)/lt_table_common.h $(CSRC)/lt_joint.h include/lt_lattice.h include/lt_align.h include/lt_sample.h include/lt_expect.h include/lt_posterior.h include/lt_string_expect.h include/lt_paths.h include/lt_beam.h
+DEPS := $(CSRC)/lt_kernels.h $(CSRC)/lt_table_common.h $(CSRC)/lt_string_common.h $(CSRC)/lt_joint.h include/lt_lattice.h include/lt_align.h include/lt_sample.h include/lt_expect.h include/lt_posterior.h include/lt_string_expect.h include/lt_paths.h include/lt_beam.h
 
 CPULIB := last_torch_amd/liblt_lattice_cpu.so
 CXX ?= g++
@@ -30,67 +30,7 @@ $(OBJ)/lt_inst_%.o: $(CSRC)/lt_inst.hip $(DEPS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -DLT_LG=$(call lg_of,$*) -DLT_LGN=$(call lgn_of,$*) -DLT_P=$(call p_of,$*) -c -o $@ $<
 
-$(OBJ)/lt_lattice.o: $(CSRC)/lt_lattice.hip $(DEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-$(OBJ)/lt_pipe.o: $(CSRC)/lt_pipe.hip $(DEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-$(OBJ)/lt_table.o: $(CSRC)/lt_table.hip $(DEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-$(OBJ)/lt_align.o: $(CSRC)/lt_align.hip $(DEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-$(OBJ)/lt_align_post.o: $(CSRC)/lt_align_post.hip $(DEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-$(OBJ)/lt_align_expect.o: $(CSRC)/lt_align_expect.hip $(DEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-$(OBJ)/lt_sample.o: $(CSRC)/lt_sample.hip $(DEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-$(OBJ)/lt_beam.o: $(CSRC)/lt_beam.hip $(DEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-$(OBJ)/lt_paths.o: $(CSRC)/lt_paths.hip $(DEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-$(OBJ)/lt_edit.o: $(CSRC)/lt_edit.hip $(DEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-$(OBJ)/lt_expect.o: $(CSRC)/lt_expect.hip $(DEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-$(OBJ)/lt_chunk.o: $(CSRC)/lt_chunk.hip $(DEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-$(OBJ)/lt_tri.o: $(CSRC)/lt_tri.hip $(DEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-$(OBJ)/lt_vit.o: $(CSRC)/lt_vit.hip $(DEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-$(OBJ)/lt_producer.o: $(CSRC)/lt_producer.hip $(DEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-$(OBJ)/lt_joint.o: $(CSRC)/lt_joint.hip $(DEPS)
+$(OBJ)/%.o: $(CSRC)/%.hip $(DEPS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 

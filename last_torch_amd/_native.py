@@ -533,6 +533,28 @@ def _tproblem(graph, W, max_labels=0):
   return TableProblem(B, T, max_labels, LT_DTYPE_BF16 if W.dtype == torch.bfloat16 else LT_DTYPE_F32)
 
 
+def _workspace(symbol, graph, pb, W, *extra, alloc=True, at_least=0):
+  """Asks lib().<symbol>(graph, pb, *extra, &bytes) for the workspace size and
+  allocates it on W's device: (bytes, uint8 tensor of max(bytes, at_least)
+  elements, or None when that is 0 or alloc is false)."""
+  nbytes = ctypes.c_size_t(0)
+  _check(getattr(lib(), symbol)(ctypes.byref(graph.g), ctypes.byref(pb), *extra,
+                                ctypes.byref(nbytes)), symbol)
+  n = max(nbytes.value, at_least)
+  ws = torch.empty([n], dtype=torch.uint8, device=W.device) if alloc and n else None
+  return nbytes.value, ws
+
+
+def _supported(symbol, graph, pb, *extra):
+  """Whether lib().<symbol>(graph, pb, *extra) takes the problem: False on
+  LT_EUNSUPPORTED, other errors raise."""
+  rc = getattr(lib(), symbol)(ctypes.byref(graph.g), ctypes.byref(pb), *extra)
+  if rc == LT_EUNSUPPORTED:
+    return False
+  _check(rc, symbol)
+  return True
+
+
 def table_forward(graph, W, num_frames, semiring, want_alpha=True):
   """lt_table_forward: (dist [B], alpha [B,T,C] or None)."""
   pb = _tproblem(graph, W)
@@ -558,18 +580,14 @@ def table_loss_grad(graph, W, num_frames, labels, num_labels, local_norm, want_g
   """lt_table_loss_grad: (loss, log_z, num, dW = d(sum loss)/dW or None)."""
   pb = _tproblem(graph, W, labels.shape[-1])
   B = W.shape[0]
-  nbytes = ctypes.c_size_t(0)
-  _check(lib().lt_table_loss_grad_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
-                                                  ctypes.byref(nbytes)),
-         'lt_table_loss_grad_workspace_bytes')
-  ws = (torch.empty([max(nbytes.value, 1)], dtype=torch.uint8, device=W.device)
-        if want_grad else None)
+  nbytes, ws = _workspace('lt_table_loss_grad_workspace_bytes', graph, pb, W, alloc=want_grad,
+                          at_least=1)
   loss, log_z, num = _f32([B], W), _f32([B], W), _f32([B], W)
   dW = torch.empty_like(W) if want_grad else None
   _check(lib().lt_table_loss_grad(ctypes.byref(graph.g), ctypes.byref(pb), int(bool(local_norm)),
                                   _ptr(W), _ptr(num_frames), _ptr(labels), _ptr(num_labels),
                                   _ptr(loss), _ptr(log_z), _ptr(num), _ptr(dW), _ptr(ws),
-                                  nbytes.value if want_grad else 0, _stream()),
+                                  nbytes if want_grad else 0, _stream()),
          'lt_table_loss_grad')
   return loss, log_z, num, dW
 
@@ -580,11 +598,8 @@ def table_den_backward(graph, W, num_frames, semiring, dist=None, alpha=None, gr
   log_z and alpha; Real: alpha * beta'; MaxTropical: the best path's arcs)."""
   pb = _tproblem(graph, W)
   B = W.shape[0]
-  nbytes = ctypes.c_size_t(0)
-  _check(lib().lt_table_den_backward_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
-                                                     semiring, ctypes.byref(nbytes)),
-         'lt_table_den_backward_workspace_bytes')
-  ws = torch.empty([max(nbytes.value, 1)], dtype=torch.uint8, device=W.device)
+  nbytes, ws = _workspace('lt_table_den_backward_workspace_bytes', graph, pb, W, semiring,
+                          at_least=1)
   dW = torch.empty_like(W)
   if dist is not None:
     dist = dist.to(torch.float32).contiguous()
@@ -594,7 +609,7 @@ def table_den_backward(graph, W, num_frames, semiring, dist=None, alpha=None, gr
     grad = grad.to(device=W.device, dtype=torch.float32).reshape(B).contiguous()
   _check(lib().lt_table_den_backward(ctypes.byref(graph.g), ctypes.byref(pb), semiring, _ptr(W),
                                      _ptr(num_frames), _ptr(dist), _ptr(alpha), _ptr(grad),
-                                     _ptr(dW), _ptr(ws), nbytes.value, _stream()),
+                                     _ptr(dW), _ptr(ws), nbytes, _stream()),
          'lt_table_den_backward')
   return dW
 
@@ -604,10 +619,7 @@ def table_num_backward_check(graph, W, labels, semiring):
   this problem (its string-gradient LDS rule, the semiring): a host-only
   query, no launch."""
   pb = _tproblem(graph, W, labels.shape[-1])
-  nbytes = ctypes.c_size_t(0)
-  _check(lib().lt_table_num_backward_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
-                                                     semiring, ctypes.byref(nbytes)),
-         'lt_table_num_backward_workspace_bytes')
+  _workspace('lt_table_num_backward_workspace_bytes', graph, pb, W, semiring, alloc=False)
 
 
 def table_num_backward(graph, W, num_frames, labels, num_labels, semiring, grad=None):
@@ -617,18 +629,15 @@ def table_num_backward(graph, W, num_frames, labels, num_labels, semiring, grad=
   acceptor)."""
   pb = _tproblem(graph, W, labels.shape[-1])
   B = W.shape[0]
-  nbytes = ctypes.c_size_t(0)
-  _check(lib().lt_table_num_backward_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
-                                                     semiring, ctypes.byref(nbytes)),
-         'lt_table_num_backward_workspace_bytes')
-  ws = torch.empty([max(nbytes.value, 1)], dtype=torch.uint8, device=W.device)
+  nbytes, ws = _workspace('lt_table_num_backward_workspace_bytes', graph, pb, W, semiring,
+                          at_least=1)
   num = _f32([B], W)
   dW = torch.empty_like(W)
   if grad is not None:
     grad = grad.to(device=W.device, dtype=torch.float32).reshape(B).contiguous()
   _check(lib().lt_table_num_backward(ctypes.byref(graph.g), ctypes.byref(pb), semiring, _ptr(W),
                                      _ptr(num_frames), _ptr(labels), _ptr(num_labels), _ptr(grad),
-                                     _ptr(num), _ptr(dW), _ptr(ws), nbytes.value, _stream()),
+                                     _ptr(num), _ptr(dW), _ptr(ws), nbytes, _stream()),
          'lt_table_num_backward')
   return num, dW
 
@@ -637,16 +646,12 @@ def table_viterbi(graph, W, num_frames, label_convention):
   """lt_table_viterbi: (labels int64 [B, T*A], path weights [B])."""
   pb = _tproblem(graph, W)
   B, T = W.shape[:2]
-  nbytes = ctypes.c_size_t(0)
-  _check(lib().lt_table_viterbi_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
-                                                ctypes.byref(nbytes)),
-         'lt_table_viterbi_workspace_bytes')
-  ws = torch.empty([max(nbytes.value, 1)], dtype=torch.uint8, device=W.device)
+  nbytes, ws = _workspace('lt_table_viterbi_workspace_bytes', graph, pb, W, at_least=1)
   labels = torch.empty([B, T * graph.num_alignment_states()], dtype=torch.int64, device=W.device)
   weight = _f32([B], W)
   _check(lib().lt_table_viterbi(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W),
                                 _ptr(num_frames), label_convention, _ptr(labels), _ptr(weight),
-                                _ptr(ws), nbytes.value, _stream()), 'lt_table_viterbi')
+                                _ptr(ws), nbytes, _stream()), 'lt_table_viterbi')
   return labels, weight
 
 
@@ -657,13 +662,8 @@ def table_align_supported(graph, W, labels):
   """Whether lt_table_align takes this problem (U <= 255, K <= 15): a
   host-only query, no launch. Other errors raise."""
   pb = _tproblem(graph, W, labels.shape[-1])
-  nbytes = ctypes.c_size_t(0)
-  rc = lib().lt_table_align_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
-                                            ctypes.byref(nbytes))
-  if rc == LT_EUNSUPPORTED:
-    return False
-  _check(rc, 'lt_table_align_workspace_bytes')
-  return True
+  return _supported('lt_table_align_workspace_bytes', graph, pb,
+                    ctypes.byref(ctypes.c_size_t(0)))
 
 
 def table_align(graph, W, num_frames, labels, num_labels):
@@ -674,17 +674,13 @@ def table_align(graph, W, num_frames, labels, num_labels):
   pb = _tproblem(graph, W, labels.shape[-1])
   B, T = W.shape[:2]
   U = labels.shape[-1]
-  nbytes = ctypes.c_size_t(0)
-  _check(lib().lt_table_align_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
-                                              ctypes.byref(nbytes)),
-         'lt_table_align_workspace_bytes')
-  ws = (torch.empty([nbytes.value], dtype=torch.uint8, device=W.device) if nbytes.value else None)
+  nbytes, ws = _workspace('lt_table_align_workspace_bytes', graph, pb, W)
   out = torch.empty([B, T * graph.num_alignment_states()], dtype=torch.int64, device=W.device)
   frames = torch.empty([B, U], dtype=torch.int64, device=W.device)
   weight = _f32([B], W)
   _check(lib().lt_table_align(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W), _ptr(num_frames),
                               _ptr(labels), _ptr(num_labels), _ptr(out), _ptr(frames),
-                              _ptr(weight), _ptr(ws), nbytes.value, _stream()), 'lt_table_align')
+                              _ptr(weight), _ptr(ws), nbytes, _stream()), 'lt_table_align')
   return out, frames, weight
 
 
@@ -692,13 +688,8 @@ def table_align_posteriors_supported(graph, W, labels):
   """Whether lt_table_align_posteriors takes this problem (FrameDependent,
   U <= 255): a host-only query, no launch. Other errors raise."""
   pb = _tproblem(graph, W, labels.shape[-1])
-  nbytes = ctypes.c_size_t(0)
-  rc = lib().lt_table_align_posteriors_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
-                                                       ctypes.byref(nbytes))
-  if rc == LT_EUNSUPPORTED:
-    return False
-  _check(rc, 'lt_table_align_posteriors_workspace_bytes')
-  return True
+  return _supported('lt_table_align_posteriors_workspace_bytes', graph, pb,
+                    ctypes.byref(ctypes.c_size_t(0)))
 
 
 def table_align_posteriors(graph, W, num_frames, labels, num_labels):
@@ -709,16 +700,12 @@ def table_align_posteriors(graph, W, num_frames, labels, num_labels):
   pb = _tproblem(graph, W, labels.shape[-1])
   B, T = W.shape[:2]
   U = labels.shape[-1]
-  nbytes = ctypes.c_size_t(0)
-  _check(lib().lt_table_align_posteriors_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
-                                                         ctypes.byref(nbytes)),
-         'lt_table_align_posteriors_workspace_bytes')
-  ws = (torch.empty([nbytes.value], dtype=torch.uint8, device=W.device) if nbytes.value else None)
+  nbytes, ws = _workspace('lt_table_align_posteriors_workspace_bytes', graph, pb, W)
   emission = _f32([B, T, U], W)
   log_prob = _f32([B], W)
   _check(lib().lt_table_align_posteriors(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W),
                                          _ptr(num_frames), _ptr(labels), _ptr(num_labels),
-                                         _ptr(emission), _ptr(log_prob), _ptr(ws), nbytes.value,
+                                         _ptr(emission), _ptr(log_prob), _ptr(ws), nbytes,
                                          _stream()), 'lt_table_align_posteriors')
   return emission, log_prob
 
@@ -728,13 +715,8 @@ def table_align_expectation_supported(graph, W, labels):
   this problem (FrameDependent, U <= 255): a host-only query, no launch. Other
   errors raise."""
   pb = _tproblem(graph, W, labels.shape[-1])
-  nbytes = ctypes.c_size_t(0)
-  rc = lib().lt_table_align_expectation_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
-                                                        ctypes.byref(nbytes))
-  if rc == LT_EUNSUPPORTED:
-    return False
-  _check(rc, 'lt_table_align_expectation_workspace_bytes')
-  return True
+  return _supported('lt_table_align_expectation_workspace_bytes', graph, pb,
+                    ctypes.byref(ctypes.c_size_t(0)))
 
 
 def table_align_expectation(graph, W, lexical_values, blank_values, num_frames, labels,
@@ -756,12 +738,8 @@ def table_align_expectation(graph, W, lexical_values, blank_values, num_frames, 
                      f'[{B}, {T}, {U + 1}]')
   lexical_values = lexical_values.to(device=W.device, dtype=torch.float32).contiguous()
   blank_values = blank_values.to(device=W.device, dtype=torch.float32).contiguous()
-  nbytes = ctypes.c_size_t(0)
-  _check(lib().lt_table_align_expectation_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
-                                                          ctypes.byref(nbytes)),
-         'lt_table_align_expectation_workspace_bytes')
-  ws = (torch.empty([nbytes.value], dtype=torch.uint8, device=W.device)
-        if nbytes.value and (want_post or want_cov) else None)
+  nbytes, ws = _workspace('lt_table_align_expectation_workspace_bytes', graph, pb, W,
+                          alloc=want_post or want_cov)
   expected, log_prob = _f32([B], W), _f32([B], W)
   emission = _f32([B, T, U], W) if want_post else None
   blank_occ = _f32([B, T, U + 1], W) if want_post else None
@@ -771,7 +749,7 @@ def table_align_expectation(graph, W, lexical_values, blank_values, num_frames, 
       ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W), _ptr(lexical_values), _ptr(blank_values),
       _ptr(num_frames), _ptr(labels), _ptr(num_labels), _ptr(expected), _ptr(log_prob),
       _ptr(emission), _ptr(blank_occ), _ptr(cov_lex), _ptr(cov_blank), _ptr(ws),
-      nbytes.value if ws is not None else 0, _stream()), 'lt_table_align_expectation')
+      nbytes if ws is not None else 0, _stream()), 'lt_table_align_expectation')
   return expected, log_prob, emission, blank_occ, cov_lex, cov_blank
 
 
@@ -804,11 +782,7 @@ def table_sample(graph, W, num_frames, log_z, alpha, num_samples, seed):
   pb = _tproblem(graph, W)
   B, T = W.shape[:2]
   S = int(num_samples)
-  nbytes = ctypes.c_size_t(0)
-  _check(lib().lt_table_sample_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb), S,
-                                               ctypes.byref(nbytes)),
-         'lt_table_sample_workspace_bytes')
-  ws = (torch.empty([nbytes.value], dtype=torch.uint8, device=W.device) if nbytes.value else None)
+  nbytes, ws = _workspace('lt_table_sample_workspace_bytes', graph, pb, W, S)
   log_z = log_z.to(torch.float32).contiguous()
   alpha = alpha.to(torch.float32).contiguous()
   if tuple(alpha.shape) != (B, T, graph.C) or tuple(log_z.shape) != (B,):
@@ -818,7 +792,7 @@ def table_sample(graph, W, num_frames, log_z, alpha, num_samples, seed):
   weight = _f32([B, S], W)
   _check(lib().lt_table_sample(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W), _ptr(num_frames),
                                _ptr(log_z), _ptr(alpha), S, int(seed) & 0xffffffffffffffff,
-                               _ptr(labels), _ptr(weight), _ptr(ws), nbytes.value, _stream()),
+                               _ptr(labels), _ptr(weight), _ptr(ws), nbytes, _stream()),
          'lt_table_sample')
   return labels, weight
 
@@ -828,13 +802,8 @@ def table_beam_search_supported(graph, W, beam_size):
   beam_size <= 64, V <= 1023): a host-only query, no launch. Other errors
   raise."""
   pb = _tproblem(graph, W)
-  nbytes = ctypes.c_size_t(0)
-  rc = lib().lt_table_beam_search_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
-                                                  int(beam_size), ctypes.byref(nbytes))
-  if rc == LT_EUNSUPPORTED:
-    return False
-  _check(rc, 'lt_table_beam_search_workspace_bytes')
-  return True
+  return _supported('lt_table_beam_search_workspace_bytes', graph, pb, int(beam_size),
+                    ctypes.byref(ctypes.c_size_t(0)))
 
 
 def table_beam_search(graph, W, num_frames, beam_size, semiring, want_trace=False):
@@ -846,23 +815,20 @@ def table_beam_search(graph, W, num_frames, beam_size, semiring, want_trace=Fals
   pb = _tproblem(graph, W)
   B, T = W.shape[:2]
   K = int(beam_size)
-  nbytes = ctypes.c_size_t(0)
-  _check(lib().lt_table_beam_search_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb), K,
-                                                    ctypes.byref(nbytes)),
-         'lt_table_beam_search_workspace_bytes')
+  # the workspace holds the backpointers of a call without a trace
+  nbytes, ws = _workspace('lt_table_beam_search_workspace_bytes', graph, pb, W, K,
+                          alloc=not want_trace)
   labels = torch.empty([B, K, T], dtype=torch.int64, device=W.device)
   num_labels = torch.empty([B, K], dtype=torch.int32, device=W.device)
   scores = _f32([B, K], W)
-  trace = step = ws = None
+  trace = step = None
   if want_trace:
     trace = torch.empty([B, T, K], dtype=torch.int32, device=W.device)
     step = _f32([B, T, K], W)
-  elif nbytes.value:  # the backpointers of a call without a trace
-    ws = torch.empty([nbytes.value], dtype=torch.uint8, device=W.device)
   _check(lib().lt_table_beam_search(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W),
                                     _ptr(num_frames), K, semiring, _ptr(labels),
                                     _ptr(num_labels), _ptr(scores), _ptr(trace), _ptr(step),
-                                    _ptr(ws), nbytes.value if ws is not None else 0, _stream()),
+                                    _ptr(ws), nbytes if ws is not None else 0, _stream()),
          'lt_table_beam_search')
   out = (labels, num_labels, scores)
   return out + (trace, step) if want_trace else out
@@ -883,12 +849,8 @@ def table_path_score_supported(graph, W, num_paths):
   raise."""
   pb = _tproblem(graph, W)
   pb.batch = 0
-  rc = lib().lt_table_path_score(ctypes.byref(graph.g), ctypes.byref(pb), None, None, None,
-                                 int(num_paths), None, None, None)
-  if rc == LT_EUNSUPPORTED:
-    return False
-  _check(rc, 'lt_table_path_score')
-  return True
+  return _supported('lt_table_path_score', graph, pb, None, None, None, int(num_paths), None,
+                    None, None)
 
 
 def table_path_score(graph, W, num_frames, labels, want_states=True):
@@ -973,17 +935,13 @@ def table_expectation(graph, W, values, num_frames, want_marg=True, want_cov=Tru
     raise ValueError(f'values {tuple(values.shape)} do not match the arc weights '
                      f'{tuple(W.shape)}')
   values = values.to(device=W.device, dtype=torch.float32).contiguous()
-  nbytes = ctypes.c_size_t(0)
-  _check(lib().lt_table_expectation_workspace_bytes(ctypes.byref(graph.g), ctypes.byref(pb),
-                                                    ctypes.byref(nbytes)),
-         'lt_table_expectation_workspace_bytes')
-  ws = torch.empty([max(nbytes.value, 1)], dtype=torch.uint8, device=W.device)
+  nbytes, ws = _workspace('lt_table_expectation_workspace_bytes', graph, pb, W, at_least=1)
   expected, log_z = _f32([B], W), _f32([B], W)
   marg = _f32(tuple(W.shape), W) if want_marg else None
   cov = _f32(tuple(W.shape), W) if want_cov else None
   _check(lib().lt_table_expectation(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W),
                                     _ptr(values), _ptr(num_frames), _ptr(expected), _ptr(log_z),
-                                    _ptr(marg), _ptr(cov), _ptr(ws), nbytes.value, _stream()),
+                                    _ptr(marg), _ptr(cov), _ptr(ws), nbytes, _stream()),
          'lt_table_expectation')
   return expected, log_z, marg, cov
 

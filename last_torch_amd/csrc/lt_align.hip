@@ -6,10 +6,10 @@
 // launch, for any next-state table.
 //
 // One wave (one 64-thread workgroup) per utterance; no wave waits for another.
-//   prologue   labels to LDS, one lane walks the context states (the table
-//              staged in LDS while it is small), every lane keeps the two
-//              weight offsets of its P = ceil((U+1)/64) consecutive string
-//              positions in registers
+//   prologue   string_prologue (lt_string_common.h): labels to LDS, one lane
+//              walks the context states (the table staged in LDS while it is
+//              small), every lane keeps the two weight offsets of its
+//              P = ceil((U+1)/64) consecutive string positions in registers
 //   forward    alpha in registers; a frame is P adds per term, one DPP wave
 //              shift of each lane's top position to its neighbour and one
 //              ballot per position slice: the winning term of (t, u) is one
@@ -26,7 +26,7 @@
 // table_oracle.c frame_max's: FrameDependent takes the blank term when
 // x >= y, FrameLabelDependent the smallest expansion count; fp32 sums in the
 // same order, so the path weight is bit-equal to lt_table_num_forward's.
-#include "lt_kernels.h"
+#include "lt_string_common.h"
 
 namespace {
 
@@ -47,20 +47,11 @@ struct AArgs {
   int chunk;      // frames staged per chunk of the backtrace (!dec_lds)
 };
 
-constexpr int kAlignLds = 160 * 1024;
 constexpr int kAlignChunk = 32 * 1024;  // bytes of decisions staged per chunk
-constexpr int kAlignTab = 32 * 1024;    // largest next-state table staged in LDS
-
-// lane l gets v of lane l-1 (lane 0: fill)
-LT_DEVINL float a_prev(float v, float fill) {
-  return __int_as_float(
-      __builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x138, 0xF, 0xF, false));
-}
 
 template <bool BF16, int P, bool FLD>
 __global__ __launch_bounds__(64) void align_kernel(const AArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char a_sm[];
-  constexpr int SP = 64 * P;              // string positions the wave holds
   constexpr int D = P == 4 ? 8 : 16;      // frames of weights in flight
   constexpr int ES = BF16 ? 2 : 4;
   const int lane = threadIdx.x, b = blockIdx.x;
@@ -68,11 +59,6 @@ __global__ __launch_bounds__(64) void align_kernel(const AArgs a) {
   const int A = FLD ? K + 1 : 1;
   const int NPL = FLD ? a.planes : 1;
   const int NW = NPL * P;                 // decision words per frame
-  int* ctx = (int*)a_sm;                  // [SP] context state of position u, times R
-  int* yn = ctx + SP;                     // [SP] label class of the arc leaving u
-  int* yt = yn + SP;                      // [SP] its true label (0: epsilon)
-  unsigned long long* dec = (unsigned long long*)(yt + SP);  // decisions / chunk
-  int* tab = (int*)dec;                   // the staged table (prologue only)
   int nf = a.nfr[b];
   nf = nf < 0 ? 0 : (nf > T ? T : nf);
 
@@ -84,36 +70,10 @@ __global__ __launch_bounds__(64) void align_kernel(const AArgs a) {
     for (int i = lane; i < U; i += 64) lfr[i] = -1;
 
   // ---- string positions: context state and label class
-  for (int u = lane; u < SP; u += 64) {
-    int y = u < U ? a.labels[(long long)b * U + u] : 0;
-    if (y < 0 || y > a.V) y = 0;
-    yt[u] = y;
-  }
-  if (a.stage_tab)
-    for (int i = lane; i < a.C * a.V; i += 64) tab[i] = a.table[i];
-  __syncthreads();
-  if (lane == 0) {
-    // positions past U repeat U's state with label class 1: loads in range
-    auto walk = [&](const int* tb) {
-      int c = 0;
-      for (int u = 0; u < SP; ++u) {
-        const int y = yt[u];
-        ctx[u] = c * a.R;
-        yn[u] = y < 1 ? 1 : y;
-        if (y != 0) c = tb[c * a.V + y - 1];
-      }
-    };
-    if (a.stage_tab) walk(tab);
-    else walk(a.table);
-  }
-  __syncthreads();
   int ob[P], ol[P];
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    ob[j] = ctx[lane * P + j];
-    ol[j] = ob[j] + yn[lane * P + j];
-  }
-  __syncthreads();  // the table's image is dead: decisions may overwrite it
+  const StringLds sl = string_prologue<P, 64, 0>(a, b, lane, lane, a_sm, ob, ol);
+  const int* yt = sl.yt;
+  unsigned long long* dec = (unsigned long long*)sl.region;  // decisions / chunk
 
   // ---- forward
   const long long FR = (long long)a.C * a.R;
@@ -159,7 +119,7 @@ __global__ __launch_bounds__(64) void align_kernel(const AArgs a) {
         float lo[P];
 #pragma unroll
         for (int j = 0; j < P; ++j) lo[j] = al[j] + wl[j];
-        const float up = a_prev(lo[P - 1], -kInf);
+        const float up = wave_prev(lo[P - 1], -kInf);
 #pragma unroll
         for (int j = 0; j < P; ++j) {
           const float x = al[j] + wb[j];
@@ -183,7 +143,7 @@ __global__ __launch_bounds__(64) void align_kernel(const AArgs a) {
           float lo[P];
 #pragma unroll
           for (int j = 0; j < P; ++j) lo[j] = L[j] + wl[j];
-          const float up = a_prev(lo[P - 1], -kInf);
+          const float up = wave_prev(lo[P - 1], -kInf);
 #pragma unroll
           for (int j = 0; j < P; ++j) {
             // L_i[u] = L_{i-1}[u-1] + lex[u-1]; -inf below position i
@@ -276,63 +236,26 @@ __global__ __launch_bounds__(64) void align_kernel(const AArgs a) {
   }
 }
 
-int a_fail(int code, const char* msg) { return lt_impl::set_error(code, msg); }
-
-struct AlignPlan {
-  int P, planes, NW;
-  int dec_lds, stage_tab, chunk;
-  int lds;
-  size_t ws;
+struct AlignPlan : StringPlan {
+  int planes, NW, chunk;
 };
 
 // Validates the shape and lays out LDS / workspace.
 int align_plan(const lt_graph* g, const lt_table_problem* pb, AlignPlan* pl) {
-  if (!g || !pb) return a_fail(LT_EINVAL, "null graph / problem");
-  if (g->num_states < 1 || g->vocab_size < 1 || g->expansions < 0)
-    return a_fail(LT_EINVAL, "bad graph (states >= 1, vocab >= 1, expansions >= 0)");
-  if (!g->next_state) return a_fail(LT_EINVAL, "null graph arrays");
-  if (pb->batch < 0 || pb->max_frames < 0 || pb->max_labels < 0)
-    return a_fail(LT_EINVAL, "negative shape");
-  if (pb->weight_dtype != LT_DTYPE_F32 && pb->weight_dtype != LT_DTYPE_BF16)
-    return a_fail(LT_EINVAL, "bad dtype");
-  if (pb->max_labels > 255) return a_fail(LT_EUNSUPPORTED, "lt_table_align: max_labels > 255");
-  if (g->expansions > 15) return a_fail(LT_EUNSUPPORTED, "lt_table_align: expansions > 15");
-  if ((long long)g->num_states * (g->vocab_size + 1) > 0x7fffffffLL)
-    return a_fail(LT_EUNSUPPORTED, "lt_table_align: a frame of 2^31 weights or more");
-  const int S = pb->max_labels + 1;
-  pl->P = S <= 64 ? 1 : (S <= 128 ? 2 : 4);
+  if (int rc = table_check("lt_table_align", g, pb, kChkString, [&] {
+        if (pb->max_labels > 255) return fail(LT_EUNSUPPORTED, "lt_table_align: max_labels > 255");
+        if (g->expansions > 15) return fail(LT_EUNSUPPORTED, "lt_table_align: expansions > 15");
+        return LT_OK;
+      }))
+    return rc;
+  pl->P = string_positions(pb->max_labels);
   pl->planes = 1;
   while ((1 << pl->planes) < g->expansions + 1) ++pl->planes;
   pl->NW = pl->planes * pl->P;
-  const long long fixed = 3LL * 4 * 64 * pl->P;
-  const long long tabb = 4LL * g->num_states * g->vocab_size;
-  pl->stage_tab = tabb <= kAlignTab ? 1 : 0;
-  const long long stage = pl->stage_tab ? tabb : 0;
-  const long long decb = 8LL * pl->NW * pb->max_frames;
-  pl->dec_lds = fixed + std::max(decb, stage) <= kAlignLds ? 1 : 0;
   pl->chunk = std::max(1, kAlignChunk / (8 * pl->NW));
-  const long long region = pl->dec_lds ? decb : 8LL * pl->NW * pl->chunk;
-  pl->lds = (int)(fixed + ((std::max(region, stage) + 15) & ~15LL));
-  pl->ws = pl->dec_lds ? 0 : (size_t)(((long long)pb->batch * decb + 255) & ~255LL);
+  // ctx, yn, yt; a frame of decisions is NW words
+  string_layout(g, pb, 3LL * 4 * 64 * pl->P, 8LL * pl->NW, 8LL * pl->NW * pl->chunk, pl);
   return LT_OK;
-}
-
-template <bool BF16, int P>
-int align_launch_p(const AArgs& a, int lds, hipStream_t st) {
-  auto k = a.K > 0 ? align_kernel<BF16, P, true> : align_kernel<BF16, P, false>;
-  if (lds > 64 * 1024)
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
-        hipSuccess)
-      return a_fail(LT_EHIP, "alignment LDS");
-  hipLaunchKernelGGL(k, dim3(a.B), dim3(64), lds, st, a);
-  return hipGetLastError() == hipSuccess ? LT_OK : a_fail(LT_EHIP, "alignment kernel launch");
-}
-
-template <bool BF16>
-int align_launch(const AArgs& a, const AlignPlan& pl, hipStream_t st) {
-  if (pl.P == 1) return align_launch_p<BF16, 1>(a, pl.lds, st);
-  if (pl.P == 2) return align_launch_p<BF16, 2>(a, pl.lds, st);
-  return align_launch_p<BF16, 4>(a, pl.lds, st);
 }
 
 }  // namespace
@@ -355,14 +278,14 @@ int lt_table_align(const lt_graph* g, const lt_table_problem* pb, const void* W,
   if (pb->batch == 0) return LT_OK;
   if ((!W && pb->max_frames > 0) || !num_frames || !num_labels || !path_weight ||
       (!alignment_labels && pb->max_frames > 0) || (pb->max_labels > 0 && !labels))
-    return a_fail(LT_EINVAL, "null pointer");
+    return fail(LT_EINVAL, "null pointer");
   const bool bf16 = pb->weight_dtype == LT_DTYPE_BF16;
   if (((uintptr_t)W & (bf16 ? 1 : 3)) || ((uintptr_t)num_frames & 3) || ((uintptr_t)labels & 3) ||
       ((uintptr_t)num_labels & 3) || ((uintptr_t)alignment_labels & 7) ||
       ((uintptr_t)label_frames & 7) || ((uintptr_t)path_weight & 3) || ((uintptr_t)workspace & 7))
-    return a_fail(LT_EINVAL, "misaligned pointer");
+    return fail(LT_EINVAL, "misaligned pointer");
   if (pl.ws && (!workspace || workspace_bytes < pl.ws))
-    return a_fail(LT_EINVAL, "workspace too small");
+    return fail(LT_EINVAL, "workspace too small");
   AArgs a;
   memset(&a, 0, sizeof(a));
   a.W = (const unsigned char*)W;
@@ -382,11 +305,16 @@ int lt_table_align(const lt_graph* g, const lt_table_problem* pb, const void* W,
   a.R = g->vocab_size + 1;
   a.K = g->expansions;
   a.planes = pl.planes;
-  a.dec_lds = pl.dec_lds;
+  a.dec_lds = pl.hist_lds;
   a.stage_tab = pl.stage_tab;
   a.chunk = pl.chunk;
   hipStream_t st = (hipStream_t)stream;
-  return bf16 ? align_launch<true>(a, pl, st) : align_launch<false>(a, pl, st);
+  return dispatch(bf16, pl.P, [&](auto bf, auto p) {
+    constexpr bool BF16 = decltype(bf)::value;
+    constexpr int P = decltype(p)::value;
+    auto k = a.K > 0 ? align_kernel<BF16, P, true> : align_kernel<BF16, P, false>;
+    return launch(k, dim3(a.B), dim3(64), pl.lds, st, a, "alignment");
+  });
 }
 
 }  // extern "C"

@@ -7,14 +7,16 @@
 // lt_table_align_expectation: ONE launch, one 128-thread workgroup per
 // utterance. Wave F runs (alpha, abar) upward from frame 0, wave R runs (beta,
 // bbar) downward from frame nf-1, and they meet once, at m = nf/2.
-//   prologue   lt_align_post.hip's, unchanged: labels to LDS, one lane walks
-//              the context states, every lane of both waves keeps the two
-//              weight offsets of its P = ceil((U+1)/64) positions in registers
+//   prologue   string_prologue's (lt_string_common.h), kept as this kernel's
+//              own code: labels to LDS, one lane walks the context states,
+//              every lane of both waves keeps the two weight offsets of its
+//              P = ceil((U+1)/64) positions in registers
 //   phase 1    F stores (alpha_t, abar_t) for t < m, R stores (beta_{t+1},
 //              bbar_{t+1}) for t >= m into the history [T, 3, 64P]: per
 //              position (integer part, fraction) and the mean. A value-only
 //              call keeps no history.
-//   midpoint   both waves publish their vectors in LDS, ONE workgroup barrier,
+//   midpoint   string_midpoint (lt_string_common.h) with the means: both waves
+//              publish their vectors in LDS, ONE workgroup barrier,
 //              then both compute log_prob = logsumexp_u(alpha_m[u] + beta_m[u])
 //              and expected = sum_u p_m[u] (abar_m[u] + bbar_m[u]) from the
 //              same LDS words by the same instructions: bit-equal in both
@@ -34,7 +36,7 @@
 // lt_table_string_scatter: one kernel. A workgroup owns kScatFrames rows of
 // one utterance's dW: it zeroes them, and behind a workgroup barrier writes
 // one sum per chain-head cell (the rule of tab_bwd_num_k0_body, lt_table.hip).
-#include "lt_kernels.h"
+#include "lt_string_common.h"
 
 namespace {
 
@@ -56,19 +58,6 @@ struct XArgs {
   int B, T, U, C, V, R;
   int stage_tab;       // the next-state table is staged in LDS for the walk
 };
-
-constexpr int kExpLds = 160 * 1024;
-constexpr int kExpTab = 32 * 1024;  // largest next-state table staged in LDS
-
-// lane l gets v of lane l-1 (lane 0: fill) / of lane l+1 (lane 63: fill)
-LT_DEVINL float x_prev(float v, float fill) {
-  return __int_as_float(
-      __builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x138, 0xF, 0xF, false));
-}
-LT_DEVINL float x_next(float v, float fill) {
-  return __int_as_float(
-      __builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x130, 0xF, 0xF, false));
-}
 
 // lae_split (lt_kernels.h) with the conditional means of its two terms: the
 // result's mean is the softmax-weighted mean of ma and mb, the weights 1 /
@@ -193,8 +182,8 @@ LT_DEVINL void exp_phase(const XArgs& a, const unsigned char* wbase, long long f
         }
         if constexpr (PH2) {
           // beta_{t+1}[u+1]: the row's next column (column 64P is never a live arc)
-          const float nxo = x_next(hh[0].x, -kInf), nxf = x_next(hh[0].y, 0.f);
-          const float nxm = x_next(hm[0], 0.f);
+          const float nxo = wave_next(hh[0].x, -kInf), nxf = wave_next(hh[0].y, 0.f);
+          const float nxm = wave_next(hm[0], 0.f);
 #pragma unroll
           for (int j = 0; j < P; ++j) {
             const float ro = j == P - 1 ? nxo : hh[j == P - 1 ? j : j + 1].x;
@@ -206,8 +195,8 @@ LT_DEVINL void exp_phase(const XArgs& a, const unsigned char* wbase, long long f
             kb[j] = eb[j] > 0.f ? eb[j] * ((bm[j] + hm[j]) - E) : 0.f;
           }
         }
-        const float po = x_prev(o[P - 1], -kInf), pf = x_prev(lf[P - 1], 0.f);
-        const float pq = x_prev(lm[P - 1], 0.f);
+        const float po = wave_prev(o[P - 1], -kInf), pf = wave_prev(lf[P - 1], 0.f);
+        const float pq = wave_prev(lm[P - 1], 0.f);
 #pragma unroll
         for (int j = 0; j < P; ++j) {
           const int u = lane * P + j;
@@ -221,8 +210,8 @@ LT_DEVINL void exp_phase(const XArgs& a, const unsigned char* wbase, long long f
           }
         }
       } else {
-        const float nxo = x_next(o[0], -kInf), nxv = x_next(v[0], 0.f);
-        const float nxm = x_next(mn[0], 0.f);
+        const float nxo = wave_next(o[0], -kInf), nxv = wave_next(v[0], 0.f);
+        const float nxm = wave_next(mn[0], 0.f);
 #pragma unroll
         for (int j = 0; j < P; ++j) {
           const int u = lane * P + j;
@@ -361,43 +350,11 @@ __global__ __launch_bounds__(128) void align_expect_kernel(const XArgs a) {
   else
     exp_phase<BF16, P, true, false>(a, wbase, FRB, lvb, bvb, ob, ol, o, v, mn, hist, obl, obb,
                                     keep, U, nlc, lane, 0, n1, nf, 0.f, 0.f, 0.f);
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    mid[(rev ? SP : 0) + lane * P + j] = make_float2(o[j], v[j]);
-    midm[(rev ? SP : 0) + lane * P + j] = mn[j];
-  }
-  __syncthreads();  // the one meeting of the two waves: history rows and the midpoint vectors
 
-  // ---- log_prob = logsumexp_u(alpha_m[u] + beta_m[u]) and expected = the
-  // posterior mean of abar_m[u] + bbar_m[u], the same in both waves
-  float si[P], sf[P], sm[P];
-  float mx = -kInf;
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    const float2 x = mid[lane * P + j], y = mid[SP + lane * P + j];
-    si[j] = x.x + y.x;
-    sf[j] = x.y + y.y;
-    sm[j] = midm[lane * P + j] + midm[SP + lane * P + j];
-    mx = fmaxf(mx, si[j] + sf[j]);
-  }
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
-  const bool ok = __builtin_isfinite(mx);  // wave-uniform, and the same in both waves
-  const float lpi = ok ? floorf(mx) : 0.f;
-  float sum = 0.f, ex = 0.f;
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    const float e = lt_exp((si[j] - lpi) + sf[j]);
-    sum += e;
-    ex += e > 0.f ? e * sm[j] : 0.f;
-  }
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) {
-    sum += __shfl_xor(sum, s, 64);
-    ex += __shfl_xor(ex, s, 64);
-  }
-  const float lpf = lt_log_acc(sum);
-  const float E = ok ? ex / sum : 0.f;
+  // ---- the one meeting of the two waves: log_prob and expected = the
+  // posterior mean of abar_m[u] + bbar_m[u], the same in both
+  float lpi, lpf, E;
+  const bool ok = string_midpoint<P, true>(mid, midm, rev, lane, o, v, mn, lpi, lpf, E);
   if (tid == 0) {
     a.lp[b] = ok ? lpi + lpf : -kInf;
     a.expected[b] = E;
@@ -466,18 +423,7 @@ __global__ __launch_bounds__(kScatThreads) void string_scatter_kernel(const SArg
   float* dw = a.dW + (long long)b * a.T * FR;
   const int t0 = blockIdx.x * kScatFrames;
   const int tz = t0 + kScatFrames < a.T ? t0 + kScatFrames : a.T;
-  {  // ---- zeros over the workgroup's rows: to 16-byte alignment, 16-byte stores, the tail
-    float* z = dw + (long long)t0 * FR;
-    const long long n = (long long)(tz - t0) * FR;
-    const long long peel = (long long)(((16 - ((uintptr_t)z & 15)) & 15) / 4);
-    const long long hd = peel < n ? peel : n;
-    if (tid < hd) z[tid] = 0.f;
-    float4* z4 = (float4*)(z + hd);
-    const long long n4 = (n - hd) / 4;
-    for (long long i = tid; i < n4; i += kScatThreads) z4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    const long long done = hd + 4 * n4;
-    if (done + tid < n) z[done + tid] = 0.f;
-  }
+  zero_rows(dw + (long long)t0 * FR, (long long)(tz - t0) * FR, tid, kScatThreads);
   const int t1 = tz < nf ? tz : nf;
   if (t0 >= t1) return;  // workgroup-uniform: padding frames stay zero
   int nl = a.nlab[b];
@@ -526,76 +472,26 @@ __global__ __launch_bounds__(kScatThreads) void string_scatter_kernel(const SArg
   }
 }
 
-int xp_fail(int code, const char* msg) { return lt_impl::set_error(code, msg); }
-
-struct ExpPlan {
-  int P, hist_lds, stage_tab, lds;
-  size_t ws;
-};
-
-// Validates the graph and the shape (shared by both entry points).
-int string_check(const lt_graph* g, const lt_table_problem* pb, const char* unsup_k,
-                 const char* unsup_u, const char* unsup_w) {
-  if (!g || !pb) return xp_fail(LT_EINVAL, "null graph / problem");
-  if (g->num_states < 1 || g->vocab_size < 1 || g->expansions < 0)
-    return xp_fail(LT_EINVAL, "bad graph (states >= 1, vocab >= 1, expansions >= 0)");
-  if (!g->next_state) return xp_fail(LT_EINVAL, "null graph arrays");
-  if (pb->batch < 0 || pb->max_frames < 0 || pb->max_labels < 0)
-    return xp_fail(LT_EINVAL, "negative shape");
-  if (g->expansions > 0) return xp_fail(LT_EUNSUPPORTED, unsup_k);
-  if (pb->max_labels > 255) return xp_fail(LT_EUNSUPPORTED, unsup_u);
-  if ((long long)g->num_states * (g->vocab_size + 1) > 0x7fffffffLL)
-    return xp_fail(LT_EUNSUPPORTED, unsup_w);
-  return LT_OK;
+// The refusals both entry points make (flags: how the entry looks at the dtype).
+int string_check(const char* entry, const lt_graph* g, const lt_table_problem* pb, int flags) {
+  return table_check(entry, g, pb, kChkString | flags, [&] {
+    if (g->expansions > 0)
+      return fail(LT_EUNSUPPORTED,
+                  std::string(entry) + ": FrameLabelDependent (expansions >= 1)");
+    if (pb->max_labels > 255)
+      return fail(LT_EUNSUPPORTED, std::string(entry) + ": max_labels > 255");
+    return LT_OK;
+  });
 }
 
 // Validates the shape and lays out LDS / workspace.
-int exp_plan(const lt_graph* g, const lt_table_problem* pb, ExpPlan* pl) {
-  if (int rc = string_check(
-          g, pb, "lt_table_align_expectation: FrameLabelDependent (expansions >= 1)",
-          "lt_table_align_expectation: max_labels > 255",
-          "lt_table_align_expectation: a frame of 2^31 weights or more"))
-    return rc;
-  if (pb->weight_dtype != LT_DTYPE_F32 && pb->weight_dtype != LT_DTYPE_BF16)
-    return xp_fail(LT_EINVAL, "bad dtype");
-  const int S = pb->max_labels + 1;
-  pl->P = S <= 64 ? 1 : (S <= 128 ? 2 : 4);
+int exp_plan(const lt_graph* g, const lt_table_problem* pb, StringPlan* pl) {
+  if (int rc = string_check("lt_table_align_expectation", g, pb, kChkDtypeLast)) return rc;
+  pl->P = string_positions(pb->max_labels);
   const long long SP = 64LL * pl->P;
-  const long long fixed = 3 * 4 * SP + 2 * 12 * SP;  // ctx, yn, yt; the two midpoint triples
-  const long long tabb = 4LL * g->num_states * g->vocab_size;
-  pl->stage_tab = tabb <= kExpTab ? 1 : 0;
-  const long long stage = pl->stage_tab ? tabb : 0;
-  const long long histb = 12 * SP * pb->max_frames;
-  pl->hist_lds = fixed + std::max(histb, stage) <= kExpLds ? 1 : 0;
-  const long long region = std::max(pl->hist_lds ? histb : 0LL, stage);
-  pl->lds = (int)(fixed + ((region + 15) & ~15LL));
-  pl->ws = pl->hist_lds ? 0 : (size_t)(((long long)pb->batch * histb + 255) & ~255LL);
+  // ctx, yn, yt; the two midpoint triples; a frame of history is a triple a position
+  string_layout(g, pb, 3 * 4 * SP + 2 * 12 * SP, 12 * SP, 0, pl);
   return LT_OK;
-}
-
-template <bool BF16, int P, bool HL>
-int exp_launch_k(const XArgs& a, int lds, hipStream_t st) {
-  auto k = align_expect_kernel<BF16, P, HL>;
-  if (lds > 64 * 1024)
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
-        hipSuccess)
-      return xp_fail(LT_EHIP, "alignment expectation LDS");
-  hipLaunchKernelGGL(k, dim3(a.B), dim3(128), lds, st, a);
-  return hipGetLastError() == hipSuccess ? LT_OK
-                                         : xp_fail(LT_EHIP, "alignment expectation kernel launch");
-}
-
-template <bool BF16, int P>
-int exp_launch_p(const XArgs& a, const ExpPlan& pl, hipStream_t st) {
-  return pl.hist_lds ? exp_launch_k<BF16, P, true>(a, pl.lds, st)
-                     : exp_launch_k<BF16, P, false>(a, pl.lds, st);
-}
-
-template <bool BF16>
-int exp_launch(const XArgs& a, const ExpPlan& pl, hipStream_t st) {
-  if (pl.P == 1) return exp_launch_p<BF16, 1>(a, pl, st);
-  if (pl.P == 2) return exp_launch_p<BF16, 2>(a, pl, st);
-  return exp_launch_p<BF16, 4>(a, pl, st);
 }
 
 }  // namespace
@@ -604,7 +500,7 @@ extern "C" {
 
 int lt_table_align_expectation_workspace_bytes(const lt_graph* g, const lt_table_problem* pb,
                                                size_t* bytes) {
-  ExpPlan pl;
+  StringPlan pl;
   if (int rc = exp_plan(g, pb, &pl)) return rc;
   if (bytes) *bytes = pl.ws;
   return LT_OK;
@@ -617,7 +513,7 @@ int lt_table_align_expectation(const lt_graph* g, const lt_table_problem* pb, co
                                float* emission, float* blank_occ, float* cov_lex,
                                float* cov_blank, void* workspace, size_t workspace_bytes,
                                void* stream) {
-  ExpPlan pl;
+  StringPlan pl;
   if (int rc = exp_plan(g, pb, &pl)) return rc;
   if (pb->batch == 0) return LT_OK;
   const bool frames = pb->max_frames > 0;
@@ -625,17 +521,17 @@ int lt_table_align_expectation(const lt_graph* g, const lt_table_problem* pb, co
   if ((!W && frames) || !num_frames || !num_labels || !expected || !log_prob ||
       (!lexical_values && frames && pb->max_labels > 0) || (!blank_values && frames) ||
       (pb->max_labels > 0 && !labels))
-    return xp_fail(LT_EINVAL, "null pointer");
+    return fail(LT_EINVAL, "null pointer");
   const bool bf16 = pb->weight_dtype == LT_DTYPE_BF16;
   if (((uintptr_t)W & (bf16 ? 1 : 3)) || ((uintptr_t)lexical_values & 3) ||
       ((uintptr_t)blank_values & 3) || ((uintptr_t)num_frames & 3) || ((uintptr_t)labels & 3) ||
       ((uintptr_t)num_labels & 3) || ((uintptr_t)expected & 3) || ((uintptr_t)log_prob & 3) ||
       ((uintptr_t)emission & 3) || ((uintptr_t)blank_occ & 3) || ((uintptr_t)cov_lex & 3) ||
       ((uintptr_t)cov_blank & 3) || ((uintptr_t)workspace & 7))
-    return xp_fail(LT_EINVAL, "misaligned pointer");
+    return fail(LT_EINVAL, "misaligned pointer");
   // a value-only call keeps no history
   if (keep && pl.ws && (!workspace || workspace_bytes < pl.ws))
-    return xp_fail(LT_EINVAL, "workspace too small");
+    return fail(LT_EINVAL, "workspace too small");
   XArgs a;
   memset(&a, 0, sizeof(a));
   a.W = (const unsigned char*)W;
@@ -660,23 +556,25 @@ int lt_table_align_expectation(const lt_graph* g, const lt_table_problem* pb, co
   a.R = g->vocab_size + 1;
   a.stage_tab = pl.stage_tab;
   hipStream_t st = (hipStream_t)stream;
-  return bf16 ? exp_launch<true>(a, pl, st) : exp_launch<false>(a, pl, st);
+  return dispatch(bf16, pl.P, [&](auto bf, auto p) {
+    constexpr bool BF16 = decltype(bf)::value;
+    constexpr int P = decltype(p)::value;
+    auto k = pl.hist_lds ? align_expect_kernel<BF16, P, true> : align_expect_kernel<BF16, P, false>;
+    return launch(k, dim3(a.B), dim3(128), pl.lds, st, a, "alignment expectation");
+  });
 }
 
 int lt_table_string_scatter(const lt_graph* g, const lt_table_problem* pb, const float* g_lex,
                             const float* g_blank, const int32_t* num_frames,
                             const int32_t* labels, const int32_t* num_labels, float* dW,
                             void* stream) {
-  if (int rc = string_check(g, pb, "lt_table_string_scatter: FrameLabelDependent (expansions >= 1)",
-                            "lt_table_string_scatter: max_labels > 255",
-                            "lt_table_string_scatter: a frame of 2^31 weights or more"))
-    return rc;
+  if (int rc = string_check("lt_table_string_scatter", g, pb, kChkNoDtype)) return rc;
   if (pb->batch == 0 || pb->max_frames == 0) return LT_OK;
   if (!num_frames || !num_labels || !dW || !g_blank || (pb->max_labels > 0 && (!labels || !g_lex)))
-    return xp_fail(LT_EINVAL, "null pointer");
+    return fail(LT_EINVAL, "null pointer");
   if (((uintptr_t)g_lex & 3) || ((uintptr_t)g_blank & 3) || ((uintptr_t)num_frames & 3) ||
       ((uintptr_t)labels & 3) || ((uintptr_t)num_labels & 3) || ((uintptr_t)dW & 3))
-    return xp_fail(LT_EINVAL, "misaligned pointer");
+    return fail(LT_EINVAL, "misaligned pointer");
   SArgs a;
   memset(&a, 0, sizeof(a));
   a.gl = g_lex;
@@ -692,15 +590,13 @@ int lt_table_string_scatter(const lt_graph* g, const lt_table_problem* pb, const
   a.C = g->num_states;
   a.V = g->vocab_size;
   a.R = g->vocab_size + 1;
-  const long long tabb = 4LL * g->num_states * g->vocab_size;
-  a.stage_tab = tabb <= kExpTab ? 1 : 0;
-  hipStream_t st = (hipStream_t)stream;
+  const long long tabb = stage_table(g);
+  a.stage_tab = tabb ? 1 : 0;
   const int S = a.U + 1;
-  const int lds = 4 * (2 * S + 2 * S) + (a.stage_tab ? (int)tabb : 0);
+  const int lds = 4 * (2 * S + 2 * S) + (int)tabb;
   const int chunks = (a.T + kScatFrames - 1) / kScatFrames;
-  hipLaunchKernelGGL(string_scatter_kernel, dim3(chunks, a.B), dim3(kScatThreads), lds, st, a);
-  return hipGetLastError() == hipSuccess ? LT_OK
-                                         : xp_fail(LT_EHIP, "string scatter kernel launch");
+  return launch(string_scatter_kernel, dim3(chunks, a.B), dim3(kScatThreads), lds,
+                (hipStream_t)stream, a, "string scatter");
 }
 
 }  // extern "C"

@@ -8,16 +8,16 @@
 // One 128-thread workgroup per utterance: wave F runs alpha upward from frame
 // 0, wave R runs beta downward from frame nf-1, and they meet once, at the
 // midpoint m = nf/2.
-//   prologue   lt_align.hip's: labels to LDS, one lane walks the context
-//              states (the table staged in LDS while it is small), every
-//              lane of both waves keeps the two weight offsets of its
-//              P = ceil((U+1)/64) consecutive positions in registers
+//   prologue   string_prologue (lt_string_common.h): labels to LDS, one lane
+//              walks the context states (the table staged in LDS while it is
+//              small), every lane of both waves keeps the two weight offsets
+//              of its P = ceil((U+1)/64) consecutive positions in registers
 //   phase 1    F stores alpha_t for t < m, R stores beta_{t+1} for t >= m
 //              into the history [T, 64P] (one row per frame, written by
 //              exactly one of the two) -- in LDS while T rows fit beside the
 //              prologue's arrays, else in the caller's workspace
-//   midpoint   F publishes alpha_m and R beta_m in LDS, ONE workgroup
-//              barrier, then both waves compute
+//   midpoint   string_midpoint (lt_string_common.h): F publishes alpha_m and R
+//              beta_m in LDS, ONE workgroup barrier, then both waves compute
 //                  log_prob = logsumexp_u(alpha_m[u] + beta_m[u])
 //              from the same LDS words by the same instructions: one value,
 //              bit-equal in both waves, normalises both halves
@@ -30,7 +30,7 @@
 // [0, 1) (lae_split, lt_kernels.h) in registers AND in the history: the
 // exponent's three large terms cancel exactly in the integer parts and only
 // fractions are rounded. No atomics: a call is deterministic.
-#include "lt_kernels.h"
+#include "lt_string_common.h"
 
 namespace {
 
@@ -46,19 +46,6 @@ struct PoArgs {
   int B, T, U, C, V, R;
   int stage_tab;       // the next-state table is staged in LDS for the walk
 };
-
-constexpr int kPostLds = 160 * 1024;
-constexpr int kPostTab = 32 * 1024;  // largest next-state table staged in LDS
-
-// lane l gets v of lane l-1 (lane 0: fill) / of lane l+1 (lane 63: fill)
-LT_DEVINL float p_prev(float v, float fill) {
-  return __int_as_float(
-      __builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x138, 0xF, 0xF, false));
-}
-LT_DEVINL float p_next(float v, float fill) {
-  return __int_as_float(
-      __builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x130, 0xF, 0xF, false));
-}
 
 // Steps i0..i1-1 of one wave; step i is frame t = i (F) or nf-1-i (R). Phase
 // 1 (!PH2) stores the wave's vector before each frame into the history,
@@ -137,7 +124,7 @@ LT_DEVINL void post_phase(const unsigned char* wbase, long long frame_bytes, con
             if (u < U) er[u] = lt_exp(arg);
           }
         }
-        const float po = p_prev(o[P - 1], -kInf), pv = p_prev(lv[P - 1], 0.f);
+        const float po = wave_prev(o[P - 1], -kInf), pv = wave_prev(lv[P - 1], 0.f);
 #pragma unroll
         for (int j = 0; j < P; ++j) {
           const int u = lane * P + j;
@@ -149,7 +136,7 @@ LT_DEVINL void post_phase(const unsigned char* wbase, long long frame_bytes, con
           }
         }
       } else {
-        const float nxo = p_next(o[0], -kInf), nxv = p_next(v[0], 0.f);
+        const float nxo = wave_next(o[0], -kInf), nxv = wave_next(v[0], 0.f);
 #pragma unroll
         for (int j = 0; j < P; ++j) {
           const int u = lane * P + j;
@@ -185,12 +172,6 @@ __global__ __launch_bounds__(128) void align_post_kernel(const PoArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x;
   const bool rev = __builtin_amdgcn_readfirstlane(tid) >= 64;  // wave R
   const int U = a.U, T = a.T;
-  int* ctx = (int*)po_sm;                  // [SP] context state of position u, times R
-  int* yn = ctx + SP;                      // [SP] label class of the arc leaving u
-  int* yt = yn + SP;                       // [SP] its true label (0: epsilon)
-  float2* mid = (float2*)(yt + SP);        // [2, SP] alpha_m, beta_m
-  unsigned char* region = (unsigned char*)(mid + 2 * SP);  // staged table, then the history
-  int* tab = (int*)region;
   int nf = a.nfr[b];
   nf = nf < 0 ? 0 : (nf > T ? T : nf);
   float* em = a.em + (long long)b * T * U;
@@ -199,41 +180,14 @@ __global__ __launch_bounds__(128) void align_post_kernel(const PoArgs a) {
   for (long long i = (long long)nf * U + tid; i < (long long)T * U; i += 128) em[i] = 0.f;
 
   // ---- string positions: context state and label class
-  for (int u = tid; u < SP; u += 128) {
-    int y = u < U ? a.labels[(long long)b * U + u] : 0;
-    if (y < 0 || y > a.V) y = 0;
-    yt[u] = y;
-  }
-  if (a.stage_tab)
-    for (int i = tid; i < a.C * a.V; i += 128) tab[i] = a.table[i];
-  __syncthreads();
-  if (tid == 0) {
-    // positions past U repeat U's state with label class 1: loads in range
-    auto walk = [&](const int* tb) {
-      int c = 0;
-      for (int u = 0; u < SP; ++u) {
-        const int y = yt[u];
-        ctx[u] = c * a.R;
-        yn[u] = y < 1 ? 1 : y;
-        if (y != 0) c = tb[c * a.V + y - 1];
-      }
-    };
-    if (a.stage_tab) walk(tab);
-    else walk(a.table);
-  }
-  __syncthreads();
   int ob[P], ol[P];
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    ob[j] = ctx[lane * P + j];
-    ol[j] = ob[j] + yn[lane * P + j];
-  }
-  __syncthreads();  // the table's image is dead: the history may overwrite it
+  const StringLds sl = string_prologue<P, 128, 16>(a, b, tid, lane, po_sm, ob, ol);
+  float2* mid = (float2*)sl.mid;  // [2, SP] alpha_m, beta_m; behind them the history
 
   const long long FRB = (long long)a.C * a.R * ES;
   const unsigned char* wbase = a.W + (long long)b * T * FRB;
   float2* hist;
-  if constexpr (HL) hist = (float2*)region;
+  if constexpr (HL) hist = (float2*)sl.region;
   else hist = a.ws + (long long)b * T * SP;
   const int nlb = a.nlab[b];
   const int fin = (nlb >= 0 && nlb <= U) ? nlb : -1;
@@ -250,30 +204,11 @@ __global__ __launch_bounds__(128) void align_post_kernel(const PoArgs a) {
   // ---- phase 1
   if (!rev) post_phase<BF16, P, false, false>(wbase, FRB, ob, ol, o, v, hist, em, U, lane, 0, n1, nf, 0.f, 0.f);
   else post_phase<BF16, P, true, false>(wbase, FRB, ob, ol, o, v, hist, em, U, lane, 0, n1, nf, 0.f, 0.f);
-#pragma unroll
-  for (int j = 0; j < P; ++j) mid[(rev ? SP : 0) + lane * P + j] = make_float2(o[j], v[j]);
-  __syncthreads();  // the one meeting of the two waves: history rows and alpha_m / beta_m
 
-  // ---- log_prob = logsumexp_u(alpha_m[u] + beta_m[u]), the same in both waves
-  float si[P], sf[P];
-  float mx = -kInf;
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    const float2 x = mid[lane * P + j], y = mid[SP + lane * P + j];
-    si[j] = x.x + y.x;
-    sf[j] = x.y + y.y;
-    mx = fmaxf(mx, si[j] + sf[j]);
-  }
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
-  const bool ok = __builtin_isfinite(mx);  // wave-uniform, and the same in both waves
-  const float lpi = ok ? floorf(mx) : 0.f;
-  float sum = 0.f;
-#pragma unroll
-  for (int j = 0; j < P; ++j) sum += lt_exp((si[j] - lpi) + sf[j]);
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) sum += __shfl_xor(sum, s, 64);
-  const float lpf = lt_log_acc(sum);
+  // ---- the one meeting of the two waves: log_prob, the same in both
+  float lpi, lpf, unused;
+  const bool ok =
+      string_midpoint<P, false>(mid, nullptr, rev, lane, o, v, nullptr, lpi, lpf, unused);
   if (tid == 0) a.lp[b] = ok ? lpi + lpf : -kInf;
   if (!ok) {  // unaligned: no path carries weight
     for (long long i = tid; i < (long long)nf * U; i += 128) em[i] = 0.f;
@@ -285,67 +220,22 @@ __global__ __launch_bounds__(128) void align_post_kernel(const PoArgs a) {
   else post_phase<BF16, P, true, true>(wbase, FRB, ob, ol, o, v, hist, em, U, lane, n1, nf, nf, lpi, lpf);
 }
 
-int po_fail(int code, const char* msg) { return lt_impl::set_error(code, msg); }
-
-struct PostPlan {
-  int P, hist_lds, stage_tab, lds;
-  size_t ws;
-};
-
 // Validates the shape and lays out LDS / workspace.
-int post_plan(const lt_graph* g, const lt_table_problem* pb, PostPlan* pl) {
-  if (!g || !pb) return po_fail(LT_EINVAL, "null graph / problem");
-  if (g->num_states < 1 || g->vocab_size < 1 || g->expansions < 0)
-    return po_fail(LT_EINVAL, "bad graph (states >= 1, vocab >= 1, expansions >= 0)");
-  if (!g->next_state) return po_fail(LT_EINVAL, "null graph arrays");
-  if (pb->batch < 0 || pb->max_frames < 0 || pb->max_labels < 0)
-    return po_fail(LT_EINVAL, "negative shape");
-  if (pb->weight_dtype != LT_DTYPE_F32 && pb->weight_dtype != LT_DTYPE_BF16)
-    return po_fail(LT_EINVAL, "bad dtype");
-  if (g->expansions > 0)
-    return po_fail(LT_EUNSUPPORTED, "lt_table_align_posteriors: FrameLabelDependent (expansions >= 1)");
-  if (pb->max_labels > 255)
-    return po_fail(LT_EUNSUPPORTED, "lt_table_align_posteriors: max_labels > 255");
-  if ((long long)g->num_states * (g->vocab_size + 1) > 0x7fffffffLL)
-    return po_fail(LT_EUNSUPPORTED, "lt_table_align_posteriors: a frame of 2^31 weights or more");
-  const int S = pb->max_labels + 1;
-  pl->P = S <= 64 ? 1 : (S <= 128 ? 2 : 4);
+int post_plan(const lt_graph* g, const lt_table_problem* pb, StringPlan* pl) {
+  if (int rc = table_check("lt_table_align_posteriors", g, pb, kChkString, [&] {
+        if (g->expansions > 0)
+          return fail(LT_EUNSUPPORTED,
+                      "lt_table_align_posteriors: FrameLabelDependent (expansions >= 1)");
+        if (pb->max_labels > 255)
+          return fail(LT_EUNSUPPORTED, "lt_table_align_posteriors: max_labels > 255");
+        return LT_OK;
+      }))
+    return rc;
+  pl->P = string_positions(pb->max_labels);
   const long long SP = 64LL * pl->P;
-  const long long fixed = 3 * 4 * SP + 2 * 8 * SP;  // ctx, yn, yt; alpha_m, beta_m
-  const long long tabb = 4LL * g->num_states * g->vocab_size;
-  pl->stage_tab = tabb <= kPostTab ? 1 : 0;
-  const long long stage = pl->stage_tab ? tabb : 0;
-  const long long histb = 8 * SP * pb->max_frames;
-  pl->hist_lds = fixed + std::max(histb, stage) <= kPostLds ? 1 : 0;
-  const long long region = std::max(pl->hist_lds ? histb : 0LL, stage);
-  pl->lds = (int)(fixed + ((region + 15) & ~15LL));
-  pl->ws = pl->hist_lds ? 0 : (size_t)(((long long)pb->batch * histb + 255) & ~255LL);
+  // ctx, yn, yt; alpha_m, beta_m; a frame of history is (integer part, fraction) a position
+  string_layout(g, pb, 3 * 4 * SP + 2 * 8 * SP, 8 * SP, 0, pl);
   return LT_OK;
-}
-
-template <bool BF16, int P, bool HL>
-int post_launch_k(const PoArgs& a, int lds, hipStream_t st) {
-  auto k = align_post_kernel<BF16, P, HL>;
-  if (lds > 64 * 1024)
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
-        hipSuccess)
-      return po_fail(LT_EHIP, "alignment posteriors LDS");
-  hipLaunchKernelGGL(k, dim3(a.B), dim3(128), lds, st, a);
-  return hipGetLastError() == hipSuccess ? LT_OK
-                                         : po_fail(LT_EHIP, "alignment posteriors kernel launch");
-}
-
-template <bool BF16, int P>
-int post_launch_p(const PoArgs& a, const PostPlan& pl, hipStream_t st) {
-  return pl.hist_lds ? post_launch_k<BF16, P, true>(a, pl.lds, st)
-                     : post_launch_k<BF16, P, false>(a, pl.lds, st);
-}
-
-template <bool BF16>
-int post_launch(const PoArgs& a, const PostPlan& pl, hipStream_t st) {
-  if (pl.P == 1) return post_launch_p<BF16, 1>(a, pl, st);
-  if (pl.P == 2) return post_launch_p<BF16, 2>(a, pl, st);
-  return post_launch_p<BF16, 4>(a, pl, st);
 }
 
 }  // namespace
@@ -354,7 +244,7 @@ extern "C" {
 
 int lt_table_align_posteriors_workspace_bytes(const lt_graph* g, const lt_table_problem* pb,
                                               size_t* bytes) {
-  PostPlan pl;
+  StringPlan pl;
   if (int rc = post_plan(g, pb, &pl)) return rc;
   if (bytes) *bytes = pl.ws;
   return LT_OK;
@@ -364,20 +254,20 @@ int lt_table_align_posteriors(const lt_graph* g, const lt_table_problem* pb, con
                               const int32_t* num_frames, const int32_t* labels,
                               const int32_t* num_labels, float* emission, float* log_prob,
                               void* workspace, size_t workspace_bytes, void* stream) {
-  PostPlan pl;
+  StringPlan pl;
   if (int rc = post_plan(g, pb, &pl)) return rc;
   if (pb->batch == 0) return LT_OK;
   const bool any_em = pb->max_frames > 0 && pb->max_labels > 0;
   if ((!W && pb->max_frames > 0) || !num_frames || !num_labels || !log_prob ||
       (!emission && any_em) || (pb->max_labels > 0 && !labels))
-    return po_fail(LT_EINVAL, "null pointer");
+    return fail(LT_EINVAL, "null pointer");
   const bool bf16 = pb->weight_dtype == LT_DTYPE_BF16;
   if (((uintptr_t)W & (bf16 ? 1 : 3)) || ((uintptr_t)num_frames & 3) || ((uintptr_t)labels & 3) ||
       ((uintptr_t)num_labels & 3) || ((uintptr_t)emission & 3) || ((uintptr_t)log_prob & 3) ||
       ((uintptr_t)workspace & 7))
-    return po_fail(LT_EINVAL, "misaligned pointer");
+    return fail(LT_EINVAL, "misaligned pointer");
   if (pl.ws && (!workspace || workspace_bytes < pl.ws))
-    return po_fail(LT_EINVAL, "workspace too small");
+    return fail(LT_EINVAL, "workspace too small");
   PoArgs a;
   memset(&a, 0, sizeof(a));
   a.W = (const unsigned char*)W;
@@ -396,7 +286,12 @@ int lt_table_align_posteriors(const lt_graph* g, const lt_table_problem* pb, con
   a.R = g->vocab_size + 1;
   a.stage_tab = pl.stage_tab;
   hipStream_t st = (hipStream_t)stream;
-  return bf16 ? post_launch<true>(a, pl, st) : post_launch<false>(a, pl, st);
+  return dispatch(bf16, pl.P, [&](auto bf, auto p) {
+    constexpr bool BF16 = decltype(bf)::value;
+    constexpr int P = decltype(p)::value;
+    auto k = pl.hist_lds ? align_post_kernel<BF16, P, true> : align_post_kernel<BF16, P, false>;
+    return launch(k, dim3(a.B), dim3(128), pl.lds, st, a, "alignment posteriors");
+  });
 }
 
 }  // extern "C"

@@ -38,7 +38,7 @@
 //   trace     lane r stores (source << 16) | label of frame t, coalesced. After
 //             the last frame, behind a device-scope fence, lane r walks its
 //             chain back from frame nf-1 and writes its labels back to front.
-#include "lt_kernels.h"
+#include "lt_string_common.h"
 
 namespace {
 
@@ -61,18 +61,8 @@ struct BArgs {
 
 constexpr int kBeamKpt = 4;             // 16-byte loads a thread holds per slice
 constexpr int kBeamThreads = 512;       // workgroup of the ring kernel
-constexpr int kBeamTab = 32 * 1024;     // largest next-state table staged in LDS
 constexpr int kBeamMaxK = 64;
 constexpr int kBeamMaxV = 1023;
-
-// max over the wave, wave-uniform (the whole wave must be active)
-LT_DEVINL float wave_max(float v) {
-  v = dpp_max<0>(v);
-  v = dpp_max<1>(v);
-  v = dpp_max<2>(v);
-  v = dpp_max<3>(v);
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rows_fold<true>(v)), 63));
-}
 
 LT_DEVINL unsigned long long readlane64(unsigned long long v, int l) {
   const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
@@ -403,8 +393,6 @@ __global__ __launch_bounds__(RING ? kBeamThreads : 64) void beam_kernel(const BA
   }
 }
 
-int b_fail(int code, const char* msg) { return lt_impl::set_error(code, msg); }
-
 struct BeamPlan {
   int threads, L, capW, MW, stage_tab, lds;
   size_t trace_bytes;
@@ -412,25 +400,22 @@ struct BeamPlan {
 
 // Validates the shape and lays out the workgroup and its LDS.
 int beam_plan(const lt_graph* g, const lt_table_problem* pb, int beam_size, BeamPlan* pl) {
-  if (!g || !pb) return b_fail(LT_EINVAL, "null graph / problem");
-  if (g->num_states < 1 || g->vocab_size < 1 || g->expansions < 0)
-    return b_fail(LT_EINVAL, "bad graph (states >= 1, vocab >= 1, expansions >= 0)");
-  if (pb->batch < 0 || pb->max_frames < 0) return b_fail(LT_EINVAL, "negative shape");
-  if (pb->weight_dtype != LT_DTYPE_F32 && pb->weight_dtype != LT_DTYPE_BF16)
-    return b_fail(LT_EINVAL, "bad dtype");
-  if (beam_size < 1) return b_fail(LT_EINVAL, "lt_table_beam_search: beam_size < 1");
-  if (g->expansions >= 1)
-    return b_fail(LT_EUNSUPPORTED, "lt_table_beam_search: FrameLabelDependent is not searched");
-  if (!g->next_state) return b_fail(LT_EINVAL, "null graph arrays");
-  if (beam_size > kBeamMaxK)
-    return b_fail(LT_EUNSUPPORTED, "lt_table_beam_search: beam_size > 64 (one wave)");
-  if (g->vocab_size > kBeamMaxV) return b_fail(LT_EUNSUPPORTED, "lt_table_beam_search: V > 1023");
-  const long long C = g->num_states, V = g->vocab_size, R = V + 1;
-  if (C * R > 0x7fffffffLL)
-    return b_fail(LT_EUNSUPPORTED, "lt_table_beam_search: a frame of 2^31 weights or more");
+  if (int rc = table_check("lt_table_beam_search", g, pb, 0, [&] {
+        if (beam_size < 1) return fail(LT_EINVAL, "lt_table_beam_search: beam_size < 1");
+        if (g->expansions >= 1)
+          return fail(LT_EUNSUPPORTED, "lt_table_beam_search: FrameLabelDependent is not searched");
+        if (int rc = check_arrays(g, false)) return rc;
+        if (beam_size > kBeamMaxK)
+          return fail(LT_EUNSUPPORTED, "lt_table_beam_search: beam_size > 64 (one wave)");
+        if (g->vocab_size > kBeamMaxV)
+          return fail(LT_EUNSUPPORTED, "lt_table_beam_search: V > 1023");
+        return LT_OK;
+      }))
+    return rc;
+  const long long C = g->num_states, R = g->vocab_size + 1;
   const long long ntrace = (long long)pb->batch * pb->max_frames * beam_size;
   if (ntrace > 0x7fffffffLL)
-    return b_fail(LT_EUNSUPPORTED, "lt_table_beam_search: a trace of 2^31 elements or more");
+    return fail(LT_EUNSUPPORTED, "lt_table_beam_search: a trace of 2^31 elements or more");
   pl->trace_bytes = (size_t)ntrace * 4;
   // the ring: the most whole frames whose image, with up to 15 bytes of
   // misalignment in front, is kBeamKpt 16-byte loads a thread
@@ -444,20 +429,10 @@ int beam_plan(const lt_graph* g, const lt_table_problem* pb, int beam_size, Beam
   pl->capW = L ? (int)chunks(L * fw) : 0;
   pl->threads = L ? kBeamThreads : 64;
   pl->MW = (int)((R + 31) / 32);
-  pl->stage_tab = C * V * 4 <= kBeamTab ? 1 : 0;
-  pl->lds = 2 * 16 * pl->capW + 64 * pl->MW * 4 + 64 * 16 + (pl->stage_tab ? (int)(C * V * 4) : 0);
+  const long long tabb = stage_table(g);
+  pl->stage_tab = tabb ? 1 : 0;
+  pl->lds = 2 * 16 * pl->capW + 64 * pl->MW * 4 + 64 * 16 + (int)tabb;
   return LT_OK;
-}
-
-template <int MODE, bool BF16>
-int beam_launch(const BArgs& a, const BeamPlan& pl, hipStream_t st) {
-  auto k = a.L ? beam_kernel<MODE, BF16, true> : beam_kernel<MODE, BF16, false>;
-  if (pl.lds > 64 * 1024)
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds) !=
-        hipSuccess)
-      return b_fail(LT_EHIP, "beam search LDS");
-  hipLaunchKernelGGL(k, dim3((unsigned)a.B), dim3(pl.threads), pl.lds, st, a);
-  return hipGetLastError() == hipSuccess ? LT_OK : b_fail(LT_EHIP, "beam search kernel launch");
 }
 
 }  // namespace
@@ -480,17 +455,17 @@ int lt_table_beam_search(const lt_graph* g, const lt_table_problem* pb, const vo
   BeamPlan pl;
   if (int rc = beam_plan(g, pb, beam_size, &pl)) return rc;
   if (semiring != LT_SEMIRING_LOG && semiring != LT_SEMIRING_MAX)
-    return b_fail(LT_EINVAL, "lt_table_beam_search: the semiring is Log or MaxTropical");
+    return fail(LT_EINVAL, "lt_table_beam_search: the semiring is Log or MaxTropical");
   if (!num_labels || !scores || (!labels && pb->max_frames > 0))
-    return b_fail(LT_EINVAL, "lt_table_beam_search: null output");
+    return fail(LT_EINVAL, "lt_table_beam_search: null output");
   if (pb->batch == 0) return LT_OK;
-  if (!num_frames || (!W && pb->max_frames > 0)) return b_fail(LT_EINVAL, "null pointer");
+  if (!num_frames || (!W && pb->max_frames > 0)) return fail(LT_EINVAL, "null pointer");
   if (!trace && pl.trace_bytes > 0 && (!workspace || workspace_bytes < pl.trace_bytes))
-    return b_fail(LT_EINVAL, "lt_table_beam_search: workspace too small for a null trace");
+    return fail(LT_EINVAL, "lt_table_beam_search: workspace too small for a null trace");
   if (((uintptr_t)W & 15) || ((uintptr_t)num_frames & 3) || ((uintptr_t)labels & 7) ||
       ((uintptr_t)num_labels & 3) || ((uintptr_t)scores & 3) || ((uintptr_t)trace & 3) ||
       ((uintptr_t)step_score & 3) || ((uintptr_t)workspace & 3))
-    return b_fail(LT_EINVAL, "misaligned pointer");
+    return fail(LT_EINVAL, "misaligned pointer");
   BArgs a;
   memset(&a, 0, sizeof(a));
   a.W = (const unsigned char*)W;
@@ -512,11 +487,14 @@ int lt_table_beam_search(const lt_graph* g, const lt_table_problem* pb, const vo
   a.capW = pl.capW;
   a.MW = pl.MW;
   a.stage_tab = pl.stage_tab;
-  hipStream_t st = (hipStream_t)stream;
-  const bool bf16 = pb->weight_dtype == LT_DTYPE_BF16;
-  if (semiring == LT_SEMIRING_LOG)
-    return bf16 ? beam_launch<M_LOG, true>(a, pl, st) : beam_launch<M_LOG, false>(a, pl, st);
-  return bf16 ? beam_launch<M_MAX, true>(a, pl, st) : beam_launch<M_MAX, false>(a, pl, st);
+  return dispatch(pb->weight_dtype == LT_DTYPE_BF16, [&](auto bf) {
+    constexpr bool BF16 = decltype(bf)::value;
+    auto k = semiring == LT_SEMIRING_LOG
+                 ? (a.L ? beam_kernel<M_LOG, BF16, true> : beam_kernel<M_LOG, BF16, false>)
+                 : (a.L ? beam_kernel<M_MAX, BF16, true> : beam_kernel<M_MAX, BF16, false>);
+    return launch(k, dim3((unsigned)a.B), dim3(pl.threads), pl.lds, (hipStream_t)stream, a,
+                  "beam search");
+  });
 }
 
 }  // extern "C"

@@ -19,7 +19,7 @@
 //           lanes > 0 and a loop over the set bits.
 // Cells past n hold finite values nobody reads: a cell depends on lower cells
 // only.
-#include "lt_kernels.h"
+#include "lt_string_common.h"
 
 namespace {
 
@@ -145,13 +145,11 @@ __global__ __launch_bounds__(512) void edit_kernel(const EArgs a) {
   }
 }
 
-int e_fail(int code, const char* msg) { return lt_impl::set_error(code, msg); }
-
 template <int P>
 int edit_launch(const EArgs& a, hipStream_t st) {
   const int lds = a.wpb * 64 * P * 4;  // at most 32 KiB
-  hipLaunchKernelGGL(edit_kernel<P>, dim3((unsigned)(a.B * a.nblk)), dim3(64 * a.wpb), lds, st, a);
-  return hipGetLastError() == hipSuccess ? LT_OK : e_fail(LT_EHIP, "edit distance kernel launch");
+  return launch(edit_kernel<P>, dim3((unsigned)(a.B * a.nblk)), dim3(64 * a.wpb), lds, st, a,
+                "edit distance");
 }
 
 }  // namespace
@@ -163,18 +161,18 @@ int lt_edit_distance(int32_t batch, int32_t num_hyps, int32_t max_frames, int32_
                      const int32_t* num_labels, int32_t* distance, int32_t* hyp_length,
                      void* stream) {
   if (batch < 0 || max_frames < 0 || max_labels < 0)
-    return e_fail(LT_EINVAL, "lt_edit_distance: negative shape");
-  if (num_hyps < 1) return e_fail(LT_EINVAL, "lt_edit_distance: num_hyps < 1");
+    return fail(LT_EINVAL, "lt_edit_distance: negative shape");
+  if (num_hyps < 1) return fail(LT_EINVAL, "lt_edit_distance: num_hyps < 1");
   if ((long long)max_labels + 1 > kEditCells)
-    return e_fail(LT_EUNSUPPORTED, "lt_edit_distance: max_labels > 1023");
+    return fail(LT_EUNSUPPORTED, "lt_edit_distance: max_labels > 1023");
   if ((long long)num_hyps * batch > 0x7fffffffLL)
-    return e_fail(LT_EUNSUPPORTED, "lt_edit_distance: 2^31 hypotheses or more");
+    return fail(LT_EUNSUPPORTED, "lt_edit_distance: 2^31 hypotheses or more");
   if (batch == 0) return LT_OK;
   if (!distance || !num_labels || (!hyp && max_frames > 0) || (!ref && max_labels > 0))
-    return e_fail(LT_EINVAL, "lt_edit_distance: null pointer");
+    return fail(LT_EINVAL, "lt_edit_distance: null pointer");
   if (((uintptr_t)hyp & 7) || ((uintptr_t)num_frames & 3) || ((uintptr_t)ref & 3) ||
       ((uintptr_t)num_labels & 3) || ((uintptr_t)distance & 3) || ((uintptr_t)hyp_length & 3))
-    return e_fail(LT_EINVAL, "misaligned pointer");
+    return fail(LT_EINVAL, "misaligned pointer");
   EArgs a;
   memset(&a, 0, sizeof(a));
   a.hyp = (const long long*)hyp;

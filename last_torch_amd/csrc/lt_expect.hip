@@ -5,7 +5,8 @@
 //
 // Two kernels, one workgroup per utterance, on the frame-serial skeleton of
 // tab_fwd_k0_body / tab_bwd_den_k0_body (lt_table.hip, helpers shared through
-// lt_table_common.h): one barrier a frame, the vectors double-buffered in LDS
+// lt_table_common.h; the host checks and the launch through
+// lt_string_common.h): one barrier a frame, the vectors double-buffered in LDS
 // with Log's integer shift pending, the frame's W and values staged a frame
 // ahead while they fit, the graph's CSR / table in LDS.
 //   pair      every Log vector x (alpha, beta) travels with a linear-space
@@ -23,9 +24,7 @@
 //             consecutive elements of the row) and reduces beta and its means.
 // No atomics on memory; the only LDS atomic is the shift slot's integer max,
 // which is order-independent, so two calls give bit-equal outputs.
-#include <type_traits>
-
-#include "lt_table_common.h"
+#include "lt_string_common.h"
 
 namespace {
 
@@ -392,8 +391,6 @@ __global__ __launch_bounds__(512) void expect_bwd_kernel(const EArgs a) {
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-int e_fail(int code, const char* msg) { return lt_impl::set_error(code, msg); }
-
 struct ExpectPlan {
   int stage;             // graph and frames in LDS
   int lds_fwd, lds_bwd;  // dynamic LDS bytes
@@ -403,18 +400,14 @@ struct ExpectPlan {
 
 // Validates the shape and lays out LDS and the workspace.
 int expect_plan(const lt_graph* g, const lt_table_problem* pb, ExpectPlan* pl) {
-  if (!g || !pb) return e_fail(LT_EINVAL, "null graph / problem");
-  if (g->num_states < 1 || g->vocab_size < 1 || g->expansions < 0)
-    return e_fail(LT_EINVAL, "bad graph (states >= 1, vocab >= 1, expansions >= 0)");
-  if (pb->batch < 0 || pb->max_frames < 0) return e_fail(LT_EINVAL, "negative shape");
-  if (pb->weight_dtype != LT_DTYPE_F32 && pb->weight_dtype != LT_DTYPE_BF16)
-    return e_fail(LT_EINVAL, "bad dtype");
-  if (g->expansions >= 1)
-    return e_fail(LT_EUNSUPPORTED, "lt_table_expectation: FrameLabelDependent is not supported");
-  if (!g->next_state || !g->in_offsets || !g->in_arcs) return e_fail(LT_EINVAL, "null graph arrays");
+  if (int rc = table_check("lt_table_expectation", g, pb, 0, [&] {
+        if (g->expansions >= 1)
+          return fail(LT_EUNSUPPORTED,
+                      "lt_table_expectation: FrameLabelDependent is not supported");
+        return check_arrays(g, true);
+      }))
+    return rc;
   const long long C = g->num_states, V = g->vocab_size, FR = C * (V + 1);
-  if (FR > 0x7fffffffLL)
-    return e_fail(LT_EUNSUPPORTED, "lt_table_expectation: a frame of 2^31 weights or more");
   // the table kernels' LDS rule: frames and graph staged while the larger
   // (backward) image fits the staging budget, else only the vectors in LDS
   const long long vec_f = 4 * 4 * C, vec_b = 4 * 8 * C;
@@ -422,7 +415,7 @@ int expect_plan(const lt_graph* g, const lt_table_problem* pb, ExpectPlan* pl) {
   pl->stage = vec_b + graph + 16 * FR <= kStageBudget;
   const long long lf = pl->stage ? vec_f + graph + 16 * FR : vec_f;
   const long long lb = pl->stage ? vec_b + graph + 16 * FR : vec_b;
-  if (lb > kTabLds) return e_fail(LT_EUNSUPPORTED, "table lattice state exceeds LDS");
+  if (lb > kTabLds) return fail(LT_EUNSUPPORTED, "table lattice state exceeds LDS");
   pl->lds_fwd = (int)lf;
   pl->lds_bwd = (int)lb;
   // 8 lanes per state: 512 threads cover up to 64 states in one pass
@@ -433,27 +426,14 @@ int expect_plan(const lt_graph* g, const lt_table_problem* pb, ExpectPlan* pl) {
   return LT_OK;
 }
 
-template <typename KF>
-int expect_launch(KF k, const EArgs& a, int threads, int lds, hipStream_t st, const char* what) {
-  if (lds > 64 * 1024)
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
-        hipSuccess)
-      return e_fail(LT_EHIP, "expectation LDS");
-  hipLaunchKernelGGL(k, dim3((unsigned)a.B), dim3(threads), lds, st, a);
-  return hipGetLastError() == hipSuccess ? LT_OK : e_fail(LT_EHIP, what);
-}
-
 template <bool BF16>
 int expect_run(const EArgs& a, const ExpectPlan& pl, bool bwd, hipStream_t st) {
-  int rc = pl.stage ? expect_launch(expect_fwd_kernel<BF16, true>, a, pl.threads, pl.lds_fwd, st,
-                                    "expectation forward launch")
-                    : expect_launch(expect_fwd_kernel<BF16, false>, a, pl.threads, pl.lds_fwd, st,
-                                    "expectation forward launch");
+  const dim3 grid((unsigned)a.B), block(pl.threads);
+  auto fwd = pl.stage ? expect_fwd_kernel<BF16, true> : expect_fwd_kernel<BF16, false>;
+  const int rc = launch(fwd, grid, block, pl.lds_fwd, st, a, "expectation", " forward launch");
   if (rc || !bwd) return rc;
-  return pl.stage ? expect_launch(expect_bwd_kernel<BF16, true>, a, pl.threads, pl.lds_bwd, st,
-                                  "expectation backward launch")
-                  : expect_launch(expect_bwd_kernel<BF16, false>, a, pl.threads, pl.lds_bwd, st,
-                                  "expectation backward launch");
+  auto bk = pl.stage ? expect_bwd_kernel<BF16, true> : expect_bwd_kernel<BF16, false>;
+  return launch(bk, grid, block, pl.lds_bwd, st, a, "expectation", " backward launch");
 }
 
 }  // namespace
@@ -474,15 +454,15 @@ int lt_table_expectation(const lt_graph* g, const lt_table_problem* pb, const vo
                          size_t workspace_bytes, void* stream) {
   ExpectPlan pl;
   if (int rc = expect_plan(g, pb, &pl)) return rc;
-  if (!expected || !log_z) return e_fail(LT_EINVAL, "lt_table_expectation: null output");
+  if (!expected || !log_z) return fail(LT_EINVAL, "lt_table_expectation: null output");
   if (pb->batch == 0) return LT_OK;
   if (!num_frames || ((!W || !values) && pb->max_frames > 0))
-    return e_fail(LT_EINVAL, "null pointer");
+    return fail(LT_EINVAL, "null pointer");
   if (pl.total && (!workspace || workspace_bytes < pl.total))
-    return e_fail(LT_EINVAL, "workspace too small");
+    return fail(LT_EINVAL, "workspace too small");
   if (((uintptr_t)workspace & 3) || ((uintptr_t)values & 3) || ((uintptr_t)marg & 3) ||
       ((uintptr_t)cov & 3) || ((uintptr_t)W & (pb->weight_dtype == LT_DTYPE_BF16 ? 1 : 3)))
-    return e_fail(LT_EINVAL, "misaligned pointer");
+    return fail(LT_EINVAL, "misaligned pointer");
   const bool bwd = (marg || cov) && pb->max_frames > 0;
   EArgs a;
   memset(&a, 0, sizeof(a));
@@ -504,8 +484,9 @@ int lt_table_expectation(const lt_graph* g, const lt_table_problem* pb, const vo
   a.V = g->vocab_size;
   a.R = g->vocab_size + 1;
   hipStream_t st = (hipStream_t)stream;
-  return pb->weight_dtype == LT_DTYPE_BF16 ? expect_run<true>(a, pl, bwd, st)
-                                           : expect_run<false>(a, pl, bwd, st);
+  return dispatch(pb->weight_dtype == LT_DTYPE_BF16, [&](auto bf) {
+    return expect_run<decltype(bf)::value>(a, pl, bwd, st);
+  });
 }
 
 }  // extern "C"

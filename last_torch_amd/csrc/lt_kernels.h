@@ -290,6 +290,17 @@ LT_DEVINL float rows_fold(float v) {
   return r3;
 }
 
+// Wave shifts: lane l gets v of lane l-1 (lane 0: fill) / of lane l+1 (lane
+// 63: fill).
+LT_DEVINL float wave_prev(float v, float fill) {
+  return __int_as_float(
+      __builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x138, 0xF, 0xF, false));
+}
+LT_DEVINL float wave_next(float v, float fill) {
+  return __int_as_float(
+      __builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x130, 0xF, 0xF, false));
+}
+
 // max / sum over lanes 8k+7 (k = 0..7) of the wave, returned wave-uniform;
 // every other lane must hold the identity. row_shr:8 folds lane 7 into 15
 // of each row, rows_fold the rows; lane 63 ends with the total.

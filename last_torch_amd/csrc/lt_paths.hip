@@ -20,7 +20,7 @@
 //               owns, as lt_table_string_scatter does); one thread owns a
 //               (b, t) column of dW and adds the paths in ascending s, so arcs
 //               that paths share are summed in a fixed order without atomics.
-#include "lt_kernels.h"
+#include "lt_string_common.h"
 
 namespace {
 
@@ -39,7 +39,6 @@ struct PArgs {
 };
 
 constexpr int kPathTab = 64 * 1024;   // largest table staged in LDS
-constexpr int kPathLds = 160 * 1024;
 
 template <bool BF16>
 __global__ __launch_bounds__(512) void path_score_kernel(const PArgs a) {
@@ -137,17 +136,7 @@ __global__ __launch_bounds__(kScatterThreads) void path_scatter_kernel(const CAr
   const int tz = t0 + kScatterFrames < a.T ? t0 + kScatterFrames : a.T;
   const long long FR = (long long)a.C * a.R;
   float* z = a.dW + ((long long)b * a.T + t0) * FR;
-  {  // ---- zeros over the workgroup's rows: to 16-byte alignment, 16-byte stores, the tail
-    const long long n = (long long)(tz - t0) * FR;
-    const long long peel = (long long)(((16 - ((uintptr_t)z & 15)) & 15) / 4);
-    const long long hd = peel < n ? peel : n;
-    if (tid < hd) z[tid] = 0.f;
-    float4* z4 = (float4*)(z + hd);
-    const long long n4 = (n - hd) / 4;
-    for (long long i = tid; i < n4; i += kScatterThreads) z4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    const long long done = hd + 4 * n4;
-    if (done + tid < n) z[done + tid] = 0.f;
-  }
+  zero_rows(z, (long long)(tz - t0) * FR, tid, kScatterThreads);
   int nf = a.nfr[b];
   nf = nf < 0 ? 0 : (nf > a.T ? a.T : nf);
   if (t0 >= nf) return;  // workgroup-uniform: padding frames stay zero
@@ -167,23 +156,18 @@ __global__ __launch_bounds__(kScatterThreads) void path_scatter_kernel(const CAr
   }
 }
 
-int p_fail(int code, const char* msg) { return lt_impl::set_error(code, msg); }
-
 // The checks the two entry points share; the messages name the caller.
-int path_check(const lt_graph* g, const lt_table_problem* pb, int num_paths, const char* fld,
-               const char* wide, const char* many) {
-  if (!g || !pb) return p_fail(LT_EINVAL, "null graph / problem");
-  if (g->num_states < 1 || g->vocab_size < 1 || g->expansions < 0)
-    return p_fail(LT_EINVAL, "bad graph (states >= 1, vocab >= 1, expansions >= 0)");
-  if (pb->batch < 0 || pb->max_frames < 0) return p_fail(LT_EINVAL, "negative shape");
-  if (pb->weight_dtype != LT_DTYPE_F32 && pb->weight_dtype != LT_DTYPE_BF16)
-    return p_fail(LT_EINVAL, "bad dtype");
-  if (num_paths < 1) return p_fail(LT_EINVAL, "num_paths < 1");
-  if (g->expansions >= 1) return p_fail(LT_EUNSUPPORTED, fld);
-  if (!g->next_state) return p_fail(LT_EINVAL, "null graph arrays");
-  if ((long long)g->num_states * (g->vocab_size + 1) > 0x7fffffffLL)
-    return p_fail(LT_EUNSUPPORTED, wide);
-  if ((long long)num_paths * pb->batch > 0x7fffffffLL) return p_fail(LT_EUNSUPPORTED, many);
+int path_check(const char* entry, const lt_graph* g, const lt_table_problem* pb, int num_paths) {
+  if (int rc = table_check(entry, g, pb, 0, [&] {
+        if (num_paths < 1) return fail(LT_EINVAL, "num_paths < 1");
+        if (g->expansions >= 1)
+          return fail(LT_EUNSUPPORTED,
+                      std::string(entry) + ": FrameLabelDependent (expansions >= 1)");
+        return check_arrays(g, false);
+      }))
+    return rc;
+  if ((long long)num_paths * pb->batch > 0x7fffffffLL)
+    return fail(LT_EUNSUPPORTED, std::string(entry) + ": 2^31 paths or more");
   return LT_OK;
 }
 
@@ -195,31 +179,20 @@ struct ScorePlan {
 // per path, as many paths (at most 8) as fit next to it.
 int score_plan(const lt_graph* g, const lt_table_problem* pb, int num_paths, ScorePlan* pl) {
   const long long rowb = 4LL * (((long long)pb->max_frames + 63) & ~63LL);
-  long long tabb = 4LL * g->num_states * g->vocab_size;
-  if (tabb > kPathTab || tabb + rowb > kPathLds) tabb = 0;
-  if (rowb > kPathLds)
-    return p_fail(LT_EUNSUPPORTED, "lt_table_path_score: more frames than the LDS rows hold");
+  long long tabb = stage_table(g, kPathTab);
+  if (tabb + rowb > kTabLds) tabb = 0;
+  if (rowb > kTabLds)
+    return fail(LT_EUNSUPPORTED, "lt_table_path_score: more frames than the LDS rows hold");
   long long wpb = num_paths < 8 ? num_paths : 8;
-  while (wpb > 1 && tabb + wpb * rowb > kPathLds) --wpb;
+  while (wpb > 1 && tabb + wpb * rowb > kTabLds) --wpb;
   pl->wpb = (int)wpb;
   pl->nblk = (int)((num_paths + wpb - 1) / wpb);
   if ((long long)pl->nblk * pb->batch > 0x7fffffffLL)
-    return p_fail(LT_EUNSUPPORTED, "lt_table_path_score: 2^31 paths or more");
+    return fail(LT_EUNSUPPORTED, "lt_table_path_score: 2^31 paths or more");
   pl->Tp = (int)(rowb / 4);
   pl->stage_tab = tabb ? 1 : 0;
   pl->lds = (int)(tabb + wpb * rowb);
   return LT_OK;
-}
-
-template <bool BF16>
-int score_launch(const PArgs& a, const ScorePlan& pl, hipStream_t st) {
-  auto k = path_score_kernel<BF16>;
-  if (pl.lds > 64 * 1024)
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds) !=
-        hipSuccess)
-      return p_fail(LT_EHIP, "path score LDS");
-  hipLaunchKernelGGL(k, dim3((unsigned)(a.B * pl.nblk)), dim3(64 * pl.wpb), pl.lds, st, a);
-  return hipGetLastError() == hipSuccess ? LT_OK : p_fail(LT_EHIP, "path score kernel launch");
 }
 
 }  // namespace
@@ -229,19 +202,15 @@ extern "C" {
 int lt_table_path_score(const lt_graph* g, const lt_table_problem* pb, const void* W,
                         const int32_t* num_frames, const int64_t* labels, int32_t num_paths,
                         float* path_weight, int32_t* states, void* stream) {
-  if (int rc = path_check(g, pb, num_paths,
-                          "lt_table_path_score: FrameLabelDependent (expansions >= 1)",
-                          "lt_table_path_score: a frame of 2^31 weights or more",
-                          "lt_table_path_score: 2^31 paths or more"))
-    return rc;
+  if (int rc = path_check("lt_table_path_score", g, pb, num_paths)) return rc;
   ScorePlan pl;
   if (int rc = score_plan(g, pb, num_paths, &pl)) return rc;
   if (pb->batch == 0) return LT_OK;
   if (!path_weight || !num_frames || ((!W || !labels) && pb->max_frames > 0))
-    return p_fail(LT_EINVAL, "lt_table_path_score: null pointer");
+    return fail(LT_EINVAL, "lt_table_path_score: null pointer");
   if (((uintptr_t)W & 3) || ((uintptr_t)num_frames & 3) || ((uintptr_t)labels & 7) ||
       ((uintptr_t)path_weight & 3) || ((uintptr_t)states & 3))
-    return p_fail(LT_EINVAL, "misaligned pointer");
+    return fail(LT_EINVAL, "misaligned pointer");
   PArgs a;
   memset(&a, 0, sizeof(a));
   a.W = (const unsigned char*)W;
@@ -260,29 +229,26 @@ int lt_table_path_score(const lt_graph* g, const lt_table_problem* pb, const voi
   a.nblk = pl.nblk;
   a.Tp = pl.Tp;
   a.stage_tab = pl.stage_tab;
-  hipStream_t st = (hipStream_t)stream;
-  return pb->weight_dtype == LT_DTYPE_BF16 ? score_launch<true>(a, pl, st)
-                                           : score_launch<false>(a, pl, st);
+  return dispatch(pb->weight_dtype == LT_DTYPE_BF16, [&](auto bf) {
+    return launch(path_score_kernel<decltype(bf)::value>, dim3((unsigned)(a.B * pl.nblk)),
+                  dim3(64 * pl.wpb), pl.lds, (hipStream_t)stream, a, "path score");
+  });
 }
 
 int lt_table_path_scatter(const lt_graph* g, const lt_table_problem* pb,
                           const int32_t* num_frames, const int64_t* labels,
                           const int32_t* states, int32_t num_paths, const float* grad, float* dW,
                           void* stream) {
-  if (int rc = path_check(g, pb, num_paths,
-                          "lt_table_path_scatter: FrameLabelDependent (expansions >= 1)",
-                          "lt_table_path_scatter: a frame of 2^31 weights or more",
-                          "lt_table_path_scatter: 2^31 paths or more"))
-    return rc;
+  if (int rc = path_check("lt_table_path_scatter", g, pb, num_paths)) return rc;
   if (pb->batch == 0 || pb->max_frames == 0) return LT_OK;
   if (!num_frames || !labels || !states || !grad || !dW)
-    return p_fail(LT_EINVAL, "lt_table_path_scatter: null pointer");
+    return fail(LT_EINVAL, "lt_table_path_scatter: null pointer");
   if (((uintptr_t)num_frames & 3) || ((uintptr_t)labels & 7) || ((uintptr_t)states & 3) ||
       ((uintptr_t)grad & 3) || ((uintptr_t)dW & 3))
-    return p_fail(LT_EINVAL, "misaligned pointer");
+    return fail(LT_EINVAL, "misaligned pointer");
   const int chunks = (pb->max_frames + kScatterFrames - 1) / kScatterFrames;
   if ((long long)chunks * pb->batch > 0x7fffffffLL)
-    return p_fail(LT_EUNSUPPORTED, "lt_table_path_scatter: 2^31 workgroups or more");
+    return fail(LT_EUNSUPPORTED, "lt_table_path_scatter: 2^31 workgroups or more");
   CArgs a;
   memset(&a, 0, sizeof(a));
   a.nfr = num_frames;
@@ -297,10 +263,8 @@ int lt_table_path_scatter(const lt_graph* g, const lt_table_problem* pb,
   a.R = g->vocab_size + 1;
   a.S = num_paths;
   a.chunks = chunks;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(path_scatter_kernel, dim3((unsigned)(chunks * a.B)), dim3(kScatterThreads), 0, st,
-                     a);
-  return hipGetLastError() == hipSuccess ? LT_OK : p_fail(LT_EHIP, "path scatter kernel launch");
+  return launch(path_scatter_kernel, dim3((unsigned)(chunks * a.B)), dim3(kScatterThreads), 0,
+                (hipStream_t)stream, a, "path scatter");
 }
 
 }  // extern "C"

@@ -25,7 +25,7 @@
 //             gathered from memory, one dependent access a step; no barrier.
 //   labels    lane t % 64 keeps frame t's label; 64 frames go out as one
 //             coalesced store, and the whole wave zero-fills the padding.
-#include "lt_kernels.h"
+#include "lt_string_common.h"
 
 namespace {
 
@@ -50,7 +50,6 @@ struct SArgs {
 
 constexpr int kSampleKpt = 4;             // 16-byte loads a thread holds per slice
 constexpr int kSampleCsr = 48 * 1024;     // largest image of the in-arc CSR staged in LDS
-constexpr int kSampleLds = 160 * 1024;
 constexpr int kNoArc = 0x7fffffff;
 
 // Philox4x32-10 (Random123): word k & 3 of the block (k >> 2, t, s, b).
@@ -97,16 +96,6 @@ struct Pick {
   int p;    // its source state
   float w;  // its weight
 };
-
-// max over the wave, wave-uniform: four butterfly stages inside each DPP row,
-// rows_fold across the rows, lane 63 read back.
-LT_DEVINL float wave_max(float v) {
-  v = dpp_max<0>(v);
-  v = dpp_max<1>(v);
-  v = dpp_max<2>(v);
-  v = dpp_max<3>(v);
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rows_fold<true>(v)), 63));
-}
 
 // Folds one slice of at most 64 candidates (lane: ok, arc k from state p, in
 // the frame at wf / af) into the running best. Wave-uniform result. The whole
@@ -337,8 +326,6 @@ __global__ __launch_bounds__(512) void sample_kernel(const SArgs a) {
   if (active && lane == 0) a.pw[(long long)b * a.S + s] = wsum;
 }
 
-int s_fail(int code, const char* msg) { return lt_impl::set_error(code, msg); }
-
 struct SamplePlan {
   int wpb, nblk, threads;
   int L, capW, capA, stage_csr;
@@ -347,24 +334,19 @@ struct SamplePlan {
 
 // Validates the shape and lays out the workgroup and its LDS.
 int sample_plan(const lt_graph* g, const lt_table_problem* pb, int num_samples, SamplePlan* pl) {
-  if (!g || !pb) return s_fail(LT_EINVAL, "null graph / problem");
-  if (g->num_states < 1 || g->vocab_size < 1 || g->expansions < 0)
-    return s_fail(LT_EINVAL, "bad graph (states >= 1, vocab >= 1, expansions >= 0)");
-  if (pb->batch < 0 || pb->max_frames < 0) return s_fail(LT_EINVAL, "negative shape");
-  if (pb->weight_dtype != LT_DTYPE_F32 && pb->weight_dtype != LT_DTYPE_BF16)
-    return s_fail(LT_EINVAL, "bad dtype");
-  if (num_samples < 1) return s_fail(LT_EINVAL, "lt_table_sample: num_samples < 1");
-  if (g->expansions >= 1)
-    return s_fail(LT_EUNSUPPORTED, "lt_table_sample: FrameLabelDependent is not sampled");
-  if (!g->next_state || !g->in_offsets || !g->in_arcs) return s_fail(LT_EINVAL, "null graph arrays");
+  if (int rc = table_check("lt_table_sample", g, pb, 0, [&] {
+        if (num_samples < 1) return fail(LT_EINVAL, "lt_table_sample: num_samples < 1");
+        if (g->expansions >= 1)
+          return fail(LT_EUNSUPPORTED, "lt_table_sample: FrameLabelDependent is not sampled");
+        return check_arrays(g, true);
+      }))
+    return rc;
   const long long C = g->num_states, V = g->vocab_size, R = V + 1;
-  if (C * R > 0x7fffffffLL)
-    return s_fail(LT_EUNSUPPORTED, "lt_table_sample: a frame of 2^31 weights or more");
   pl->wpb = num_samples < 8 ? num_samples : 8;
   pl->nblk = (num_samples + pl->wpb - 1) / pl->wpb;
   if ((long long)pl->nblk * pb->batch > 0x7fffffffLL ||
       (long long)num_samples * pb->batch > 0x7fffffffLL)
-    return s_fail(LT_EUNSUPPORTED, "lt_table_sample: 2^31 samples or more");
+    return fail(LT_EUNSUPPORTED, "lt_table_sample: 2^31 samples or more");
   pl->threads = 64 * (pl->wpb < 4 ? 4 : pl->wpb);
   // the ring: the most whole frames whose image, W and alpha each with up to
   // 15 bytes of misalignment in front, is kSampleKpt 16-byte loads a thread
@@ -380,20 +362,9 @@ int sample_plan(const lt_graph* g, const lt_table_problem* pb, int num_samples, 
   pl->capA = L ? (int)chunks(L * fa) : 0;
   const long long ring = 2LL * 16 * (pl->capW + pl->capA);
   const long long csr = 8 * C + 8 * (C * V + C);  // seg + pairs
-  pl->stage_csr = csr <= kSampleCsr && ring + csr <= kSampleLds ? 1 : 0;
+  pl->stage_csr = csr <= kSampleCsr && ring + csr <= kTabLds ? 1 : 0;
   pl->lds = (int)(ring + (pl->stage_csr ? csr : 0));
   return LT_OK;
-}
-
-template <bool BF16>
-int sample_launch(const SArgs& a, const SamplePlan& pl, hipStream_t st) {
-  auto k = a.L ? sample_kernel<BF16, true> : sample_kernel<BF16, false>;
-  if (pl.lds > 64 * 1024)
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds) !=
-        hipSuccess)
-      return s_fail(LT_EHIP, "sampling LDS");
-  hipLaunchKernelGGL(k, dim3((unsigned)(a.B * pl.nblk)), dim3(pl.threads), pl.lds, st, a);
-  return hipGetLastError() == hipSuccess ? LT_OK : s_fail(LT_EHIP, "sampling kernel launch");
 }
 
 }  // namespace
@@ -417,13 +388,13 @@ int lt_table_sample(const lt_graph* g, const lt_table_problem* pb, const void* W
   SamplePlan pl;
   if (int rc = sample_plan(g, pb, num_samples, &pl)) return rc;
   if (!path_weight || (!labels && pb->max_frames > 0))
-    return s_fail(LT_EINVAL, "lt_table_sample: null output");
+    return fail(LT_EINVAL, "lt_table_sample: null output");
   if (pb->batch == 0) return LT_OK;
   if (!num_frames || !log_z || ((!W || !alpha) && pb->max_frames > 0))
-    return s_fail(LT_EINVAL, "null pointer");
+    return fail(LT_EINVAL, "null pointer");
   if (((uintptr_t)W & 15) || ((uintptr_t)alpha & 15) || ((uintptr_t)num_frames & 3) ||
       ((uintptr_t)log_z & 3) || ((uintptr_t)labels & 7) || ((uintptr_t)path_weight & 3))
-    return s_fail(LT_EINVAL, "misaligned pointer");
+    return fail(LT_EINVAL, "misaligned pointer");
   SArgs a;
   memset(&a, 0, sizeof(a));
   a.W = (const unsigned char*)W;
@@ -449,9 +420,12 @@ int lt_table_sample(const lt_graph* g, const lt_table_problem* pb, const void* W
   a.capW = pl.capW;
   a.capA = pl.capA;
   a.stage_csr = pl.stage_csr;
-  hipStream_t st = (hipStream_t)stream;
-  return pb->weight_dtype == LT_DTYPE_BF16 ? sample_launch<true>(a, pl, st)
-                                           : sample_launch<false>(a, pl, st);
+  return dispatch(pb->weight_dtype == LT_DTYPE_BF16, [&](auto bf) {
+    constexpr bool BF16 = decltype(bf)::value;
+    auto k = a.L ? sample_kernel<BF16, true> : sample_kernel<BF16, false>;
+    return launch(k, dim3((unsigned)(a.B * pl.nblk)), dim3(pl.threads), pl.lds,
+                  (hipStream_t)stream, a, "sampling");
+  });
 }
 
 }  // extern "C"

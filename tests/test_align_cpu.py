@@ -19,6 +19,7 @@ import torch
 import last_torch_amd as lt
 from last_torch_amd import _native
 from align_compact import CASES, compact, load
+from abi_graph import dummy_graph
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include',
                       'lt_lattice.h')
@@ -78,8 +79,8 @@ def test_align_host_validation_error_codes():
   buf = (ctypes.c_int64 * 64)()
   p = ctypes.c_void_p(ctypes.addressof(buf))
 
-  def graph(K=0, C=33, V=32):
-    return _native.Graph(C, V, K, p.value, p.value, p.value)
+  def graph(**kw):
+    return dummy_graph(p, **kw)
 
   def call(g, pb, W=p, nf=p, lab=p, nl=p, out=p, fr=p, w=p, ws=null, nbytes=0):
     return lib.lt_table_align(ctypes.byref(g), ctypes.byref(pb), W, nf, lab, nl, out, fr, w, ws,

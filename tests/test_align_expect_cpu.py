@@ -20,6 +20,7 @@ import last_torch_amd as lt
 from last_torch_amd import _native
 from last_torch_amd import cpu
 import align_expect_ref as ref
+from abi_graph import dummy_graph
 
 TOL = dict(rtol=1e-4, atol=1e-4)
 HEADER_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include')
@@ -230,7 +231,7 @@ def test_host_validation_needs_no_device():
   TP = _native.TableProblem
 
   def graph(K=0, C=5, V=4):
-    return _native.Graph(C, V, K, p.value, p.value, p.value)
+    return dummy_graph(p, K, C, V)
 
   def query(K, T, U):
     n = ctypes.c_size_t(123)

@@ -24,6 +24,7 @@ import last_torch_amd as lt
 from last_torch_amd import _native
 from last_torch_amd import cpu
 from align_post_ref import reference
+from abi_graph import dummy_graph
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include',
                       'lt_lattice.h')
@@ -282,8 +283,8 @@ def test_align_posteriors_host_validation_error_codes():
   buf = (ctypes.c_int64 * 64)()
   p = ctypes.c_void_p(ctypes.addressof(buf))
 
-  def graph(K=0, C=33, V=32):
-    return _native.Graph(C, V, K, p.value, p.value, p.value)
+  def graph(**kw):
+    return dummy_graph(p, **kw)
 
   def call(g, pb, W=p, nf=p, lab=p, nl=p, em=p, lp=p, ws=null, nbytes=0):
     return lib.lt_table_align_posteriors(ctypes.byref(g), ctypes.byref(pb), W, nf, lab, nl, em, lp,

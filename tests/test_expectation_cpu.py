@@ -22,6 +22,7 @@ import last_torch_amd as lt
 from last_torch_amd import _native
 from last_torch_amd import cpu
 import expect_ref as ref
+from abi_graph import dummy_graph
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include',
                       'lt_lattice.h')
@@ -182,8 +183,8 @@ def test_expectation_host_validation_error_codes():
   buf = (ctypes.c_int64 * 64)()
   p = ctypes.c_void_p((ctypes.addressof(buf) + 15) & ~15)
 
-  def graph(K=0, C=33, V=32):
-    return _native.Graph(C, V, K, p.value, p.value, p.value)
+  def graph(**kw):
+    return dummy_graph(p, **kw)
 
   TP = _native.TableProblem
   ok = TP(batch=2, max_frames=4, max_labels=0, weight_dtype=0)

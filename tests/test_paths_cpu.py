@@ -32,6 +32,7 @@ from last_torch_amd import _native
 from last_torch_amd import cpu
 import path_ref
 import sample_ref
+from abi_graph import dummy_graph
 
 INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include')
 
@@ -244,8 +245,8 @@ def test_host_validation_error_codes():
   ok = TP(batch=2, max_frames=4, max_labels=0, weight_dtype=0)
   empty = TP(batch=0, max_frames=4, max_labels=0, weight_dtype=0)
 
-  def graph(K=0, C=33, V=32):
-    return _native.Graph(C, V, K, p.value, p.value, p.value)
+  def graph(**kw):
+    return dummy_graph(p, **kw)
 
   def score(g, pb, W=p, nf=p, lab=p, S=4, pw=p, st=p):
     return lib.lt_table_path_score(ctypes.byref(g), ctypes.byref(pb), W, nf, lab, S, pw, st, null)

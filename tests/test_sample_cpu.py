@@ -25,6 +25,7 @@ import last_torch_amd as lt
 from last_torch_amd import _native
 from last_torch_amd import cpu
 import sample_ref as ref
+from abi_graph import dummy_graph
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include',
                       'lt_lattice.h')
@@ -189,8 +190,8 @@ def test_sample_host_validation_error_codes():
   buf = (ctypes.c_int64 * 64)()
   p = ctypes.c_void_p((ctypes.addressof(buf) + 15) & ~15)
 
-  def graph(K=0, C=33, V=32):
-    return _native.Graph(C, V, K, p.value, p.value, p.value)
+  def graph(**kw):
+    return dummy_graph(p, **kw)
 
   def call(g, pb, W=p, nf=p, lz=p, al=p, S=4, out=p, w=p):
     return lib.lt_table_sample(ctypes.byref(g), ctypes.byref(pb), W, nf, lz, al, S, 1, out, w,

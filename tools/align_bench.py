@@ -19,9 +19,7 @@ ONLY=bench|bf16|t2000|fld2 runs one workload.
 """
 import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
@@ -30,42 +28,8 @@ sys.path.insert(0, ROOT)
 from last_torch_amd import _native as nat  # noqa: E402
 from last_torch_amd import contexts  # noqa: E402
 from last_torch_amd.lattices import RecognitionLattice  # noqa: E402
+from _timing import BATCHES, REPS, SETTLE_S, batch_ms, medians  # noqa: E402
 
-SETTLE_S = float(os.environ.get('SETTLE_S', 1.0))
-BATCHES = int(os.environ.get('BATCHES', 7))
-REPS = int(os.environ.get('REPS', 10))
-
-
-def settle(fn):
-  t0 = time.perf_counter()
-  calls = 0
-  while time.perf_counter() - t0 < SETTLE_S:
-    fn()
-    calls += 1
-    if calls % 8 == 0:
-      torch.cuda.synchronize()
-  torch.cuda.synchronize()
-
-
-def batch_ms(fn):
-  e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)
-  e0.record()
-  for _ in range(REPS):
-    fn()
-  e1.record()
-  torch.cuda.synchronize()
-  return e0.elapsed_time(e1) / REPS
-
-
-def medians(fns):
-  """Median ms per call of each fn; batches of the fns alternate."""
-  for fn in fns:
-    settle(fn)
-  samples = [[] for _ in fns]
-  for _ in range(BATCHES):
-    for s, fn in zip(samples, fns):
-      s.append(batch_ms(fn))
-  return [statistics.median(s) for s in samples], [(min(s), max(s)) for s in samples]
 
 
 def run(name, V, n, K, B, T, U, dtype=torch.float32):

@@ -42,14 +42,10 @@ import os
 import statistics
 import subprocess
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-SETTLE_S = float(os.environ.get('SETTLE_S', 1.0))
-BATCHES = int(os.environ.get('BATCHES', 7))
-REPS = int(os.environ.get('REPS', 10))
 RESTATE_CALLS = int(os.environ.get('RESTATE_CALLS', 3))
 CHILD_TIMEOUT_S = float(os.environ.get('CHILD_TIMEOUT_S', 240))
 OUT = os.path.join(ROOT, 'profiles', 'align_expect_bench.jsonl')
@@ -61,40 +57,12 @@ WORKLOADS = {
 
 def run(name, V, n, B, T, U, dtype):
   import torch
+  from _timing import BATCHES, REPS, SETTLE_S, batch_ms, medians
   from last_torch_amd import _native as nat
   from last_torch_amd import alignments
   from last_torch_amd import contexts
   from last_torch_amd import cpu
   from last_torch_amd import lattices
-
-  def settle(fn):
-    t0 = time.perf_counter()
-    calls = 0
-    while time.perf_counter() - t0 < SETTLE_S:
-      fn()
-      calls += 1
-      if calls % 8 == 0:
-        torch.cuda.synchronize()
-    torch.cuda.synchronize()
-
-  def batch_ms(fn, reps):
-    e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)
-    e0.record()
-    for _ in range(reps):
-      fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-  def medians(fns):
-    """Median ms per call of each fn; batches of the fns alternate."""
-    for fn in fns:
-      settle(fn)
-    samples = [[] for _ in fns]
-    for _ in range(BATCHES):
-      for s, fn in zip(samples, fns):
-        s.append(batch_ms(fn, REPS))
-    return [statistics.median(s) for s in samples], [(min(s), max(s)) for s in samples]
 
   if not torch.cuda.is_available():
     raise SystemExit('align_expect_bench.py needs a ROCm GPU')

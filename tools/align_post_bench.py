@@ -25,7 +25,6 @@ import json
 import os
 import statistics
 import sys
-import time
 
 import torch
 
@@ -35,43 +34,9 @@ from last_torch_amd import _native as nat  # noqa: E402
 from last_torch_amd import alignments  # noqa: E402
 from last_torch_amd import contexts  # noqa: E402
 from last_torch_amd import cpu  # noqa: E402
+from _timing import BATCHES, REPS, SETTLE_S, batch_ms, medians  # noqa: E402
 
-SETTLE_S = float(os.environ.get('SETTLE_S', 1.0))
-BATCHES = int(os.environ.get('BATCHES', 7))
-REPS = int(os.environ.get('REPS', 10))
 RESTATE_CALLS = int(os.environ.get('RESTATE_CALLS', 3))
-
-
-def settle(fn):
-  t0 = time.perf_counter()
-  calls = 0
-  while time.perf_counter() - t0 < SETTLE_S:
-    fn()
-    calls += 1
-    if calls % 8 == 0:
-      torch.cuda.synchronize()
-  torch.cuda.synchronize()
-
-
-def batch_ms(fn, reps):
-  e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)
-  e0.record()
-  for _ in range(reps):
-    fn()
-  e1.record()
-  torch.cuda.synchronize()
-  return e0.elapsed_time(e1) / reps
-
-
-def medians(fns):
-  """Median ms per call of each fn; batches of the fns alternate."""
-  for fn in fns:
-    settle(fn)
-  samples = [[] for _ in fns]
-  for _ in range(BATCHES):
-    for s, fn in zip(samples, fns):
-      s.append(batch_ms(fn, REPS))
-  return [statistics.median(s) for s in samples], [(min(s), max(s)) for s in samples]
 
 
 def run(name, V, n, B, T, U, dtype=torch.float32):

@@ -32,7 +32,6 @@ import json
 import os
 import statistics
 import sys
-import time
 
 import torch
 
@@ -42,33 +41,10 @@ from last_torch_amd import _native as nat  # noqa: E402
 from last_torch_amd import contexts  # noqa: E402
 from last_torch_amd import cpu  # noqa: E402
 from last_torch_amd import semirings  # noqa: E402
+from _timing import BATCHES, REPS, SETTLE_S, batch_ms, settle  # noqa: E402
 
-SETTLE_S = float(os.environ.get('SETTLE_S', 1.0))
-BATCHES = int(os.environ.get('BATCHES', 7))
-REPS = int(os.environ.get('REPS', 10))
 TORCH_CALLS = int(os.environ.get('TORCH_CALLS', 2))
 BLANK_BIAS = 3.0
-
-
-def settle(fn):
-  t0 = time.perf_counter()
-  calls = 0
-  while time.perf_counter() - t0 < SETTLE_S:
-    fn()
-    calls += 1
-    if calls % 8 == 0:
-      torch.cuda.synchronize()
-  torch.cuda.synchronize()
-
-
-def batch_ms(fn, reps):
-  e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)
-  e0.record()
-  for _ in range(reps):
-    fn()
-  e1.record()
-  torch.cuda.synchronize()
-  return e0.elapsed_time(e1) / reps
 
 
 def run(V, n, B, T, K, semiring, dtype):
