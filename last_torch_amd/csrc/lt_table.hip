@@ -2360,19 +2360,32 @@ TArgs t_args(const lt_graph* g, const lt_table_problem* pb, const void* W, const
 
 // threads per utterance workgroup: the denominator reductions take 8 lanes
 // per state, so 512 threads cover up to 64 states in one pass
+// (mirrored by tests/test_gpu_table_paths.py tab_threads)
 int tab_threads(const TArgs& a) {
   const char* e = lt_impl::tune_str("LT_TAB_THREADS");
   const int t = (e && *e) ? atoi(e) : (a.C > 32 ? 512 : 256);
   return t >= 512 ? 512 : 256;
 }
 
+// Whether kernel k can have lds_bytes of dynamic LDS, taking the runtime's
+// grant of it past 64 KiB: LT_EUNSUPPORTED when not. (The runtime can refuse
+// a size that passes the first test; that is no HIP failure of the call's,
+// and its error is not left for the next launch check to find.)
+template <typename KF>
+int t_fits(KF k, int lds_bytes) {
+  if (lds_bytes > kTabLds) return t_fail(LT_EUNSUPPORTED, "table lattice state exceeds LDS");
+  if (lds_bytes > 64 * 1024 &&
+      hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) !=
+          hipSuccess) {
+    (void)hipGetLastError();
+    return t_fail(LT_EUNSUPPORTED, "table lattice state exceeds LDS (the runtime's grant)");
+  }
+  return LT_OK;
+}
+
 template <typename KF>
 int t_launch(KF k, int grid, int lds_bytes, hipStream_t st, const TArgs& a) {
-  if (lds_bytes > kTabLds) return t_fail(LT_EUNSUPPORTED, "table lattice state exceeds LDS");
-  if (lds_bytes > 64 * 1024)
-    if (int rc = t_hip(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           lds_bytes), "table LDS"))
-      return rc;
+  if (int rc = t_fits(k, lds_bytes)) return rc;
   if (grid == 0) return LT_OK;
   hipLaunchKernelGGL(k, dim3(grid), dim3(tab_threads(a)), lds_bytes, st, a);
   return t_hip(hipGetLastError(), "table kernel launch");
@@ -2380,16 +2393,15 @@ int t_launch(KF k, int grid, int lds_bytes, hipStream_t st, const TArgs& a) {
 
 template <typename KF>
 int t_launch2(KF k, int grid, int lds_bytes, hipStream_t st, const TArgs& a1, const TArgs& a2) {
-  if (lds_bytes > kTabLds) return t_fail(LT_EUNSUPPORTED, "table lattice state exceeds LDS");
-  if (lds_bytes > 64 * 1024)
-    if (int rc = t_hip(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           lds_bytes), "table LDS"))
-      return rc;
+  if (int rc = t_fits(k, lds_bytes)) return rc;
   if (grid == 0) return LT_OK;
   hipLaunchKernelGGL(k, dim3(grid), dim3(tab_threads(a1)), lds_bytes, st, a1, a2);
   return t_hip(hipGetLastError(), "table kernel launch");
 }
 
+// (fwd_lds, graph_lds and every kStageBudget predicate below are mirrored by
+// tests/test_gpu_table_paths.py, whose test_dispatch_mirror_places_every_shape
+// holds one tested shape in each regime: move the shape with the budget)
 int fwd_lds(int S) { return 4 * (4 * S) + 8 * S; }
 
 template <bool BF16, bool STG>
@@ -2420,6 +2432,7 @@ int launch_t_fwd(int sr, bool num, bool vit, const TArgs& a0, hipStream_t st) {
   // two weights per position and stages nothing)
   // (K = 0: tab_fwd_k0_body stages two frames)
   const long long staged = (long long)lds + graph_lds(a) + (a.K == 0 ? 8 : 4) * FR;
+  // (tests/test_gpu_table_paths.py fwd_staged, num_fwd_lds)
   if (!num && staged <= kStageBudget)
     return launch_t_fwd_s<BF16, true>(sr, num, vit, a, (int)staged, st);
   return launch_t_fwd_s<BF16, false>(sr, num, vit, a, lds, st);
@@ -2445,6 +2458,32 @@ GradLayout grad_layout(const lt_graph* g, const lt_table_problem* pb) {
   l.lx = l.dwf + (bf16 ? up(4 * BT * g->num_states * (g->vocab_size + 1)) : 0);
   l.lxn = l.lx + (g->expansions > 0 ? up(4 * BT * g->expansions * g->num_states) : 0);
   l.total = l.lxn + (g->expansions > 0 ? up(4 * BT * g->expansions * (pb->max_labels + 1)) : 0);
+  return l;
+}
+
+// lt_table_loss_grad's backward launch (denominator and string side by side):
+// its LDS bytes, whether the denominator stages its frames and whether the
+// FrameLabelDependent lexical dW sums fit beside them (`acc`)
+// (tests/test_gpu_table_paths.py bwd_staged, bwd_acc, loss_grad_lds_n)
+struct LossBwdLds {
+  bool staged;
+  int acc, bytes;
+};
+LossBwdLds loss_bwd_lds(const TArgs& a) {
+  const int C = a.C, S = a.U + 1, K = a.K;
+  const long long FR = (long long)C * a.R;
+  const long long lds_d = 4LL * (3 * C + (K + 1) * C);
+  // (K = 0: the one-barrier string backward double-buffers its rows, 80 S)
+  const long long lds_n = 4LL * (8 * S + (K + 1) * S) + 4LL * (2 * S + 2 * S) +
+                          4LL * (2 * S + 2 * S) + (K == 0 ? 12LL * S : 0);
+  LossBwdLds l;
+  // K = 0: the one-barrier den backward stages two frames
+  l.staged = lds_d + graph_lds(a) + (K == 0 ? 8 : 4) * FR <= kStageBudget;
+  // + the lexical dW sums of FrameLabelDependent(K > 0) when they fit too
+  l.acc = l.staged && K > 0 && lds_d + graph_lds(a) + 8 * FR <= kStageBudget;
+  const long long d =
+      l.staged ? lds_d + graph_lds(a) + ((l.acc || K == 0) ? 8 : 4) * FR : lds_d;
+  l.bytes = (int)std::min<long long>(std::max(d, lds_n), (long long)kTabLds + 1);
   return l;
 }
 
@@ -2531,6 +2570,14 @@ int lt_table_loss_grad(const lt_graph* g, const lt_table_problem* pb, int32_t lo
   const int C = a.C, S = a.U + 1, K = a.K;
   const long long FR = (long long)C * a.R;
   int rc;
+  // the backward's kernel and LDS: refused here, before the forwards are launched
+  const LossBwdLds bl = loss_bwd_lds(a);
+  void (*const bwd2)(const TArgs, const TArgs) =
+      !bl.staged ? (bf16 ? tab_bwd2_kernel<true, false> : tab_bwd2_kernel<false, false>)
+      : K > 0    ? (bf16 ? tab_bwd2_fld_kernel<true, true> : tab_bwd2_fld_kernel<false, true>)
+                 : (bf16 ? tab_bwd2_kernel<true, true> : tab_bwd2_kernel<false, true>);
+  if (dW)
+    if ((rc = t_fits(bwd2, bl.bytes))) return rc;
   // ---- forwards: denominator (log_z, alpha history) and string side by side
   TArgs ad = a, an = a;
   ad.dist = log_z;
@@ -2583,26 +2630,8 @@ int lt_table_loss_grad(const lt_graph* g, const lt_table_problem* pb, int32_t lo
   ad.nsub = nullptr;
   ad.ntab = nullptr;
   an.hist = hn;
-  const int lds_d = 4 * (3 * C + (K + 1) * C);
-  // (K = 0: the one-barrier string backward double-buffers its rows, 80 S)
-  const int lds_n = 4 * (8 * S + (K + 1) * S) + 4 * (2 * S + 2 * S) + 4 * (2 * S + 2 * S) +
-                    (K == 0 ? 12 * S : 0);
-  // K = 0: the one-barrier den backward stages two frames
-  if (lds_d + graph_lds(a) + (K == 0 ? 8 : 4) * FR <= kStageBudget) {
-    // + the lexical dW sums of FrameLabelDependent(K > 0) when they fit too
-    ad.acc = K > 0 && lds_d + graph_lds(a) + 8 * FR <= kStageBudget;
-    const int l2 =
-        std::max((int)(lds_d + graph_lds(a) + ((ad.acc || K == 0) ? 8 : 4) * FR), lds_n);
-    rc = K > 0 ? (bf16 ? t_launch2(tab_bwd2_fld_kernel<true, true>, 2 * a.B, l2, st, ad, an)
-                       : t_launch2(tab_bwd2_fld_kernel<false, true>, 2 * a.B, l2, st, ad, an))
-               : (bf16 ? t_launch2(tab_bwd2_kernel<true, true>, 2 * a.B, l2, st, ad, an)
-                       : t_launch2(tab_bwd2_kernel<false, true>, 2 * a.B, l2, st, ad, an));
-  } else {
-    const int l2 = std::max(lds_d, lds_n);
-    rc = bf16 ? t_launch2(tab_bwd2_kernel<true, false>, 2 * a.B, l2, st, ad, an)
-              : t_launch2(tab_bwd2_kernel<false, false>, 2 * a.B, l2, st, ad, an);
-  }
-  if (rc) return rc;
+  ad.acc = bl.acc;
+  if ((rc = t_launch2(bwd2, 2 * a.B, bl.bytes, st, ad, an))) return rc;
   {
     const long long n = (long long)a.B * a.T * 2 * S;
     const int blocks = (int)std::min<long long>(4096, (n + 255) / 256);
@@ -2696,6 +2725,7 @@ int lt_table_den_backward(const lt_graph* g, const lt_table_problem* pb, int32_t
     a.den_in = dist;
     a.num_in = dist;  // the den-only backward: live while the distance is finite
     const int lds_d = 4 * (3 * C + (K + 1) * C);
+    // (as loss_bwd_lds: tests/test_gpu_table_paths.py bwd_staged, bwd_acc)
     if (lds_d + graph_lds(a) + (K == 0 ? 8 : 4) * FR <= kStageBudget) {
       a.acc = K > 0 && lds_d + graph_lds(a) + 8 * FR <= kStageBudget;
       const int lds = (int)(lds_d + graph_lds(a) + ((a.acc || K == 0) ? 8 : 4) * FR);
@@ -2730,6 +2760,7 @@ static size_t str_grad_bytes(const lt_table_problem* pb, int semiring) {
 
 // LDS bytes of tab_str_grad_kernel: the string positions' rows and, for
 // MaxTropical, the decision chunk
+// (tests/test_gpu_table_paths.py str_grad_lds, str_walk_frames)
 static long long str_grad_lds(const lt_graph* g, const lt_table_problem* pb, int32_t semiring) {
   const long long S = pb->max_labels + 1, K = g->expansions;
   return 4LL * (5 * S + (9 + K + 1 + 2) * S + 4 + ((K + 1 + 3) & ~3) * 2) +
@@ -2816,6 +2847,7 @@ int lt_table_viterbi(const lt_graph* g, const lt_table_problem* pb, const void* 
   if (int rc = t_fwd(M_MAX, false, true, a, pb->weight_dtype == LT_DTYPE_BF16, st)) return rc;
   // staged walk when a frame's backpointers fit in LDS, else one thread per
   // utterance straight from global memory
+  // (tests/test_gpu_table_paths.py backtrace_chunk)
   const long long per_frame = 4LL * KK * a.C + (a.K > 0 ? a.C : 0);
   const long long arcs_bytes = 4LL * a.C * a.V;
   const long long budget = 60 * 1024;

@@ -10,6 +10,8 @@ Log values 1e-4 * max(1, |ref|); MaxTropical values and Viterbi labels
 bit-exact; dW element by element within golden_cases.marginal_scale
 (relative to the arc's own den + num marginals; the den marginals from the
 fixture's den_grad or, for random tables, golden_cases.table_den_marginals).
+The shape-selected paths of lt_table.hip (thread counts and passes, staging
+regimes, dense-bigram kernels, chunked walks) are in test_gpu_table_paths.py.
 """
 import numpy as np
 import pytest
