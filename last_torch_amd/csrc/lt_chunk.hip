@@ -65,6 +65,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <type_traits>
 
 namespace {
 
@@ -77,6 +78,8 @@ constexpr int kRec = 1248;      // floats per chunk record (whole 128-byte lines
 constexpr int kRowT = 36;       // row stride of the transposed core in a record
 constexpr int kChunkLds = 40 * 1024;  // phase C LDS per workgroup (four per CU)
 constexpr int kMargWaves = 4;   // phase C: waves per workgroup (recursions on 0-3)
+// phase C's block size: its launches pass this and its exit code counts on it
+constexpr int kMargThreads = 64 * kMargWaves;
 constexpr int kGrp = 7;         // frames per numerator group (band offsets 0..kGrp)
 constexpr float kCert = 64.f;   // phase C's per-frame certificate: log2(max alpha max beta e^c / Z)
 constexpr int kAbWaves = 3;     // ck_ab_kernel: waves per SIMD its registers allow
@@ -1444,10 +1447,16 @@ __global__ __launch_bounds__(256) void ck_combine_kernel(const CkArgs a) {
 // ---------------------------------------------------------------------------
 // C: local recursions + marginals -> dW (one workgroup per chunk)
 // ---------------------------------------------------------------------------
+// n zero elements from p on by phase C's workgroup (padding frames and
+// padding chunks: at most one chunk, so 32-bit indices). Off the live path,
+// and the one place of ck_marg_kernel that still strides by blockDim.x: with
+// kMargThreads here too the kernel no longer reads its dispatch packet, and
+// the register allocation that follows spills more SGPRs in the walks' blocks
+// of every instantiation (33 -> 37 at the bench shape, 29 -> 42 for bf16)
 template <bool BF16>
-LT_DEVINL void store_dw(void* dW, long long e, float v) {
-  if constexpr (BF16) ((unsigned short*)dW)[e] = f2bf(v);
-  else ((float*)dW)[e] = v;
+LT_DEVINL void zero_dw(unsigned char* p, int n, int tid) {
+  using elem_t = std::conditional_t<BF16, unsigned short, float>;
+  for (int e = tid; e < n; e += (int)blockDim.x) ((elem_t*)p)[e] = 0;
 }
 
 // per-frame scalars of phase C (log2): alpha's and beta's scales, the start
@@ -1465,7 +1474,7 @@ constexpr int kFlA = 1, kFlB = 2, kFlNA = 4, kFlNB = 8, kFlAll = 15, kFlNT = 16;
 // arguments, as for V < 32. ck_kernel_c picks the instantiation of the
 // plan's L and the run-time kernel for any other.
 template <bool BF16, int PPL, bool FULL, int LC = 0>
-__global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kernel(const CkArgs a) {
+__global__ __launch_bounds__(kMargThreads, kMargWaves / 2) void ck_marg_kernel(const CkArgs a) {
   static_assert(LC == 0 || FULL, "a compile-time chunk length needs V = 32");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1512,10 +1521,10 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
     }
     if (!__builtin_isfinite(nm)) g = 0.f;  // unreachable string: loss +inf, dW = 0
   }
-  const long long e0 = ((long long)b * a.T + t0) * FR;
+  // the chunk's byte offset in W and in dW
+  const long long off = ((long long)b * a.T + t0) * FR * (BF16 ? 2 : 4);
   if (t1 <= t0 || g == 0.f) {  // padding chunk / unreachable string: dW = 0
-    const long long n = (long long)(tend - t0) * FR;
-    for (long long e = tid; e < n; e += blockDim.x) store_dw<BF16>(a.dW, e0 + e, 0.f);
+    zero_dw<BF16>((unsigned char*)a.dW + off, (tend - t0) * FR, tid);
     return;
   }
   const int nt = t1 - t0;
@@ -1524,7 +1533,6 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
   // chains of the workgroups sharing a CU need not sit on the same two SIMDs
   const int role = (wave + (int)(blockIdx.x >> 3)) & 3;
   const int hs = (nt + 1) / 2;  // den alpha forms E of frames [0, hs), den beta of [hs, nt)
-  const long long off = e0 * (BF16 ? 2 : 4);
   unsigned char* wch = lds + (off & 15);
   float* xa = (float*)(lds + cOffAd);  // [L][CP] alpha_f, linear, max 1 (scale fs Ma)
   float* xb = (float*)(lds + cOffBd);  // [L][CP] beta_{f+1} of the core, linear, max 1
@@ -2132,32 +2140,63 @@ __global__ __launch_bounds__(64 * kMargWaves, kMargWaves / 2) void ck_marg_kerne
     return;
   }
   CK_STAMP(3);
-  {
-    const long long es = BF16 ? 2 : 4;
-    const long long bytes = (long long)nt * cFB;
-    unsigned char* gdst = (unsigned char*)a.dW + off;  // same byte offset as W
-    const long long head = min((long long)((16 - (off & 15)) & 15), bytes);
-    const long long body = (bytes - head) & ~15LL;
-    const unsigned char* src = wch;  // LDS image, (off & 15)-shifted like W
-    for (long long x = tid; x < head / es; x += blockDim.x) {
-      if constexpr (BF16) ((unsigned short*)gdst)[x] = ((const unsigned short*)src)[x];
-      else ((float*)gdst)[x] = ((const float*)src)[x];
+  // The exit: nothing of the workgroup can hide it (it sits behind the
+  // barrier, and the LDS is the next workgroup's only once the last read has
+  // returned), so it is one round of LDS latency where the chunk length is a
+  // compile-time constant, and 32-bit throughout (a chunk is below 64 KiB).
+  static_assert(kMargThreads == 64 * kMargWaves && kMargWaves >= 2,
+                "the exit counts on the block size both launches pass, and on two waves for the edges");
+  const int bytes = nt * (int)cFB;
+  const int head = min((16 - (int)(off & 15)) & 15, bytes);  // bytes before the first whole granule
+  const int ng = (bytes - head) >> 4;                        // whole 16-byte granules
+  unsigned char* gdst = (unsigned char*)a.dW + off;          // same byte offset as W
+  const unsigned char* src = wch;                            // LDS image, (off & 15)-shifted like W
+  if constexpr (LC > 0) {
+    // thread tid owns granules tid + kMargThreads i; every read is issued
+    // before the first store. The unaligned head and tail (at most three
+    // floats each) go beside them: lanes 0-2 of wave 0 and of wave 1.
+    static_assert(!BF16, "the compile-time chunk lengths are fp32's");
+    constexpr int NG = ((LC * kFbC + 15) / 16 + kMargThreads - 1) / kMargThreads;
+    const unsigned o = head + 16 * tid;  // this thread's first granule: one base, 32-bit offsets
+    // the edge float of this thread: wave 0 the head's, wave 1 the tail's
+    // (each below one granule, so the bounds alone pick the lanes)
+    const int el = tid < 64 ? tid : ((head + 16 * ng) >> 2) + tid - 64;
+    const bool edge = el < (tid < 64 ? head >> 2 : bytes >> 2);
+    // the reads unconditional on a clamped granule (a frame is 272 granules,
+    // so ng >= 1), the stores under the guard. dW is written once and not
+    // read again in the call: nontemporal stores leave the cache to the W
+    // that phase A read and this phase reads again (measured)
+    v4u v[NG];
+#pragma unroll
+    for (int i = 0; i < NG; ++i)
+      v[i] = *(const v4u*)(src + head + 16 * min(tid + kMargThreads * i, ng - 1));
+    const float ev = ((const float*)src)[edge ? el : 0];
+#pragma unroll
+    for (int i = 0; i < NG; ++i)
+      if (tid + kMargThreads * i < ng)
+        __builtin_nontemporal_store(v[i], (v4u*)(gdst + (o + 16u * kMargThreads * i)));
+    if (edge) ((float*)gdst)[el] = ev;
+  } else {
+    // run-time geometry: the loop stays, two granules read ahead of their stores
+    constexpr int es = BF16 ? 2 : 4;
+    using elem_t = std::conditional_t<BF16, unsigned short, float>;
+    // (head and tail are below one granule each: a lane an element, no loop)
+    if (tid < head / es) ((elem_t*)gdst)[tid] = ((const elem_t*)src)[tid];
+    const v4u* s16 = (const v4u*)(src + head);
+    v4u* d16 = (v4u*)(gdst + head);
+    for (int x = tid; x < ng; x += 2 * kMargThreads) {
+      const int x1 = x + kMargThreads;
+      const bool two = x1 < ng;
+      const v4u v0 = s16[x], v1 = s16[two ? x1 : x];
+      __builtin_nontemporal_store(v0, d16 + x);
+      if (two) __builtin_nontemporal_store(v1, d16 + x1);
     }
-    const uint4* s16 = (const uint4*)(src + head);
-    uint4* d16 = (uint4*)(gdst + head);
-    for (long long x = tid; x < body / 16; x += blockDim.x) d16[x] = s16[x];
-    for (long long x = head + body + tid * es; x < bytes; x += blockDim.x * es) {
-      if constexpr (BF16) *(unsigned short*)(gdst + x) = *(const unsigned short*)(src + x);
-      else *(float*)(gdst + x) = *(const float*)(src + x);
-    }
+    const int xt = head + 16 * ng + tid * es;
+    if (xt < bytes) *(elem_t*)(gdst + xt) = *(const elem_t*)(src + xt);
   }
   CK_STAMP(4);
   // padding frames of this chunk
-  {
-    const long long n = (long long)(tend - t1) * FR;
-    const long long base = e0 + (long long)nt * FR;
-    for (long long e = tid; e < n; e += blockDim.x) store_dw<BF16>(a.dW, base + e, 0.f);
-  }
+  zero_dw<BF16>(gdst + bytes, (tend - t1) * FR, tid);
 }
 
 }  // namespace
@@ -2517,7 +2556,7 @@ int chunk_loss_grad(const lt_problem* pb, int local_norm, const void* W, const i
   if ((rc = ck_launch_ab(a, bf16, st))) return rc;
   a.cont = 1;
   if ((rc = ck_launch(ck_kernel_c(a.PPL, bf16, a.V == 32, a), a.B + a.B * a.K,
-                      std::max(ck_lds_c(a, bf16), kWalkLdsBytes), st, a, 64 * kMargWaves)))
+                      std::max(ck_lds_c(a, bf16), kWalkLdsBytes), st, a, kMargThreads)))
     return rc;
   char* sc = (char*)scratch;
   return serial_loss(pb, local_norm, W, num_frames, labels, num_labels, a.uflag, loss, log_z, num,
@@ -2601,7 +2640,7 @@ int lt_chunk_backward(const lt_problem* pb, int32_t local_norm, const void* W,
   hipStream_t st = (hipStream_t)stream;
   const bool bf16 = pb->weight_dtype == LT_DTYPE_BF16;
   if ((rc = ck_launch(ck_kernel_c(a.PPL, bf16, a.V == 32, a), a.B * a.K, ck_lds_c(a, bf16), st, a,
-                      64 * kMargWaves)))
+                      kMargThreads)))
     return rc;
   char* sc = (char*)scratch;
   return lt_impl::serial_loss(pb, local_norm, W, num_frames, labels, num_labels, a.uflag,
