@@ -500,5 +500,7 @@ const char* lt_version(void);
 #include "lt_paths.h"
 /* Prefix beam search: the N best label sequences, likewise. */
 #include "lt_beam.h"
+/* N label strings per utterance on shared weights, with the gradient, likewise. */
+#include "lt_strings.h"
 
 #endif /* LT_LATTICE_H_ */

@@ -104,6 +104,10 @@ _SIG = {
     'lt_table_beam_search_workspace_bytes': [_G, _TP, _I32, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_beam_search': [_G, _TP, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P,
                              ctypes.c_size_t, _P],
+    'lt_table_strings_workspace_bytes': [_G, _TP, _I32, ctypes.POINTER(ctypes.c_size_t)],
+    'lt_table_strings_forward': [_G, _TP, _P, _P, _I32, _P, _P, _P, _P, ctypes.c_size_t, _I32, _P],
+    'lt_table_strings_backward': [_G, _TP, _P, _P, _I32, _P, _P, _P, _P, _P, _P, ctypes.c_size_t,
+                                  _P],
     'lt_table_path_score': [_G, _TP, _P, _P, _P, _I32, _P, _P, _P],
     'lt_table_path_scatter': [_G, _TP, _P, _P, _P, _I32, _P, _P, _P],
     'lt_edit_distance': [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
@@ -138,7 +142,8 @@ _SIG = {
 # of a label string), include/lt_string_expect.h (expected values over a label
 # string's alignments, the string scatter), include/lt_paths.h (scoring given
 # paths, the path scatter, edit distance), include/lt_beam.h (prefix beam
-# search) and include/lt_lattice.h (everything else)
+# search), include/lt_strings.h (N label strings per utterance on shared
+# weights) and include/lt_lattice.h (everything else)
 EXPORTED_ALIGN = ('lt_table_align_workspace_bytes', 'lt_table_align')
 EXPORTED_SAMPLE = ('lt_table_sample_workspace_bytes', 'lt_table_sample')
 EXPORTED_EXPECT = ('lt_table_expectation_workspace_bytes', 'lt_table_expectation')
@@ -147,10 +152,12 @@ EXPORTED_ALIGN_EXPECT = ('lt_table_align_expectation_workspace_bytes',
                          'lt_table_align_expectation', 'lt_table_string_scatter')
 EXPORTED_PATHS = ('lt_table_path_score', 'lt_table_path_scatter', 'lt_edit_distance')
 EXPORTED_BEAM = ('lt_table_beam_search_workspace_bytes', 'lt_table_beam_search')
+EXPORTED_STRINGS = ('lt_table_strings_workspace_bytes', 'lt_table_strings_forward',
+                    'lt_table_strings_backward')
 EXPORTED = (tuple(n for n in _SIG
                   if n not in (EXPORTED_ALIGN + EXPORTED_SAMPLE + EXPORTED_EXPECT +
                                EXPORTED_POSTERIOR + EXPORTED_ALIGN_EXPECT + EXPORTED_PATHS +
-                               EXPORTED_BEAM)) +
+                               EXPORTED_BEAM + EXPORTED_STRINGS)) +
             ('lt_last_error', 'lt_version'))
 
 
@@ -832,6 +839,71 @@ def table_beam_search(graph, W, num_frames, beam_size, semiring, want_trace=Fals
          'lt_table_beam_search')
   out = (labels, num_labels, scores)
   return out + (trace, step) if want_trace else out
+
+
+def _strings_args(graph, W, labels, num_labels):
+  B = W.shape[0]
+  if labels.ndim != 3 or labels.shape[0] != B or tuple(num_labels.shape) != tuple(labels.shape[:2]):
+    raise ValueError(f'labels {tuple(labels.shape)} / num_labels {tuple(num_labels.shape)} do not '
+                     f'match [{B}, N, U] / [{B}, N]')
+  if labels.shape[1] < 1:
+    raise ValueError('labels hold no hypothesis (N = 0)')
+  return (_tproblem(graph, W, labels.shape[2]),
+          labels.to(device=W.device, dtype=torch.int32).contiguous(),
+          num_labels.to(device=W.device, dtype=torch.int32).contiguous())
+
+
+def table_strings_supported(graph, W, N, U, backward=False):
+  """Whether lt_table_strings_forward (FrameDependent, N <= 64, U <= 255) and,
+  with `backward`, lt_table_strings_backward (its LDS image of a frame) take
+  this problem: host-only queries, no launch. Other errors raise."""
+  pb = _tproblem(graph, W, int(U))
+  if not _supported('lt_table_strings_workspace_bytes', graph, pb, int(N),
+                    ctypes.byref(ctypes.c_size_t(0))):
+    return False
+  if backward:
+    pb.batch = 0
+    return _supported('lt_table_strings_backward', graph, pb, None, None, int(N), None, None,
+                      None, None, None, None, 0, None)
+  return True
+
+
+def table_strings_forward(graph, W, num_frames, labels, num_labels, want_history=False):
+  """lt_table_strings_forward: the Log string weights fp32 [B, N] of labels
+  [B, N, U] / num_labels [B, N] on each utterance's one W, one launch. Returns
+  (score, workspace): with want_history the uint8 workspace
+  table_strings_backward reads, else None."""
+  pb, labels, num_labels = _strings_args(graph, W, labels, num_labels)
+  N = labels.shape[1]
+  nbytes, ws = _workspace('lt_table_strings_workspace_bytes', graph, pb, W, N, alloc=want_history)
+  score = _f32([W.shape[0], N], W)
+  _check(lib().lt_table_strings_forward(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W),
+                                        _ptr(num_frames), N, _ptr(labels), _ptr(num_labels),
+                                        _ptr(score), _ptr(ws), nbytes if ws is not None else 0,
+                                        1 if want_history else 0, _stream()),
+         'lt_table_strings_forward')
+  return score, ws
+
+
+def table_strings_backward(graph, W, num_frames, labels, num_labels, score, grad, workspace):
+  """lt_table_strings_backward: the dense fp32 dW [B,T,C,V+1] (W's shape) of
+  sum_n grad[b, n] * score[b, n], from the workspace of a
+  table_strings_forward(..., want_history=True) on the same arguments; one
+  launch that writes every element."""
+  pb, labels, num_labels = _strings_args(graph, W, labels, num_labels)
+  B, N = labels.shape[:2]
+  if tuple(score.shape) != (B, N) or tuple(grad.shape) != (B, N):
+    raise ValueError(f'score {tuple(score.shape)} / grad {tuple(grad.shape)} do not match '
+                     f'[{B}, {N}]')
+  score = score.to(device=W.device, dtype=torch.float32).contiguous()
+  grad = grad.to(device=W.device, dtype=torch.float32).contiguous()
+  dW = _f32(tuple(W.shape), W)
+  _check(lib().lt_table_strings_backward(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W),
+                                         _ptr(num_frames), N, _ptr(labels), _ptr(num_labels),
+                                         _ptr(score), _ptr(grad), _ptr(dW), _ptr(workspace),
+                                         0 if workspace is None else workspace.numel(),
+                                         _stream()), 'lt_table_strings_backward')
+  return dW
 
 
 def _path_labels(W, labels):

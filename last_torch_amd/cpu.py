@@ -54,6 +54,11 @@ MaxTropical's first-argmax rule prefers the blank, then fewer expansions.
   beam_search   (not in the reference) the N best label sequences by prefix
                                       beam search (lt_beam.h): one gather,
                                       merge and stable sort per frame
+  string_scores (not in the reference) the Log weights of N label strings per
+                                      utterance (lt_strings.h): the string
+                                      distance over a flattened batch of
+                                      hypotheses that index their utterance's
+                                      W; plain autograd
   expectation   (not in the reference) posterior mean of an arc-additive path
                                       value (lt_expect.h): the arc marginals
                                       by autograd with a graph, so the result
@@ -168,6 +173,27 @@ def _string_distance(blank: torch.Tensor, lex: torch.Tensor, nf: torch.Tensor, n
   ok = (nl >= 0) & (nl <= U)
   num = torch.gather(alpha, 1, nl.clamp(0, U).long()[:, None])[:, 0]
   return torch.where(ok, num, semiring.zeros([], W.dtype, dev))
+
+
+def string_scores(W: torch.Tensor, nf: torch.Tensor, labels: torch.Tensor, nl: torch.Tensor,
+                  context: contexts.ContextDependency) -> torch.Tensor:
+  """The Log weights [B, N] of labels [B, N, U] / nl [B, N] on each utterance's
+  W [B, T, C, V+1] (include/lt_strings.h) in torch ops: the hypotheses as a
+  flattened batch of B * N strings, each reading its utterance's W through an
+  index (W is not repeated), then _string_distance; plain autograd.
+  FrameDependent only."""
+  B, T, C, R = W.shape
+  N, U = labels.shape[1:]
+  lab = labels.reshape(B * N, U).long()
+  ctx = context.walk_states(lab).to(W.device)                      # [B*N, U+1]
+  safe = torch.where((lab >= 1) & (lab <= R - 1), lab, torch.ones_like(lab)).to(W.device)
+  utt = torch.arange(B, device=W.device).repeat_interleave(N)[:, None, None]
+  t = torch.arange(T, device=W.device)[None, :, None]
+  blank = W[utt, t, ctx[:, None, :], 0]                            # [B*N, T, U+1]
+  lex = W[utt, t, ctx[:, None, :U], safe[:, None, :]]              # [B*N, T, U]
+  nfn = nf.to(W.device).repeat_interleave(N)
+  dist = _string_distance(blank, lex, nfn, nl.reshape(B * N).to(W.device), 0, semirings.Log)
+  return dist.reshape(B, N)
 
 
 def loss(W: torch.Tensor, nf: torch.Tensor, labels: torch.Tensor, nl: torch.Tensor,

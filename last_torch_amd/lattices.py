@@ -38,6 +38,12 @@ weights once through the ``WeightFn`` plugin as a contiguous
                      (minimum-risk training from sampled paths; not in the
                      reference); backward: lt_table_path_scatter, and
                      lt_den_backward / lt_table_den_backward only at S = 1
+  string_weights  -> lt_table_strings_forward (the Log weights of N label
+                     strings per utterance on its one W; not in the reference)
+                     + lt_table_strings_backward; past their range
+                     cpu.string_scores on the device
+  nbest_risk      -> string_weights + lt_edit_distance (N-best minimum-risk
+                     training; not in the reference)
   expectation     -> lt_table_expectation (posterior mean of arc values with
                      its gradients; not in the reference), also behind
                      entropy(differentiable=True)
@@ -347,6 +353,30 @@ class _PathScoreFn(torch.autograd.Function):
     W, nf, labels, states = ctx.saved_tensors
     dW = _native.table_path_scatter(ctx.graph, W, nf, labels, states, g.float())
     return dW.to(W.dtype), None, None, None
+
+
+class _StringsFn(torch.autograd.Function):
+  """The Log weights [B, N] of N label strings per utterance
+  (include/lt_strings.h): the forward is ONE lt_table_strings_forward call
+  that, when a gradient can be asked for, keeps the alpha / beta histories in
+  its workspace; the backward is ONE lt_table_strings_backward call that sums
+  every hypothesis' occupancies, weighted by its incoming gradient, into the
+  dense dW. A second backward (retain_graph) reuses the workspace."""
+
+  @staticmethod
+  def forward(ctx, W, nf, labels, nl, graph):
+    need = ctx.needs_input_grad[0]
+    score, ws = _native.table_strings_forward(graph, W, nf, labels, nl, want_history=need)
+    ctx.graph, ctx.ws = graph, ws
+    if need:
+      ctx.save_for_backward(W, nf, labels, nl, score)
+    return score
+
+  @staticmethod
+  def backward(ctx, g):
+    W, nf, labels, nl, score = ctx.saved_tensors
+    dW = _native.table_strings_backward(ctx.graph, W, nf, labels, nl, score, g.float(), ctx.ws)
+    return dW.to(W.dtype), None, None, None, None
 
 
 class _TableNumFn(torch.autograd.Function):
@@ -999,6 +1029,107 @@ class RecognitionLattice(nn.Module, Generic[T]):
     return (self._home(risk.reshape(batch_dims), frames),
             self._home(costs.reshape(*batch_dims, S), frames),
             self._home(shaped, frames))
+
+  def _string_weights(self, W, nf, lab, nl):
+    """Log string weights [B, N] of lab [B, N, U] / nl [B, N] over prepared
+    W / nf, differentiable w.r.t. W."""
+    if W.device.type == 'cuda':
+      graph = self._graph(W.device)
+      need = torch.is_grad_enabled() and W.requires_grad
+      if _native.table_strings_supported(graph, W, lab.shape[1], lab.shape[2], backward=need):
+        return _StringsFn.apply(W, nf, lab.to(torch.int32).contiguous(), nl.to(torch.int32), graph)
+      return cpu.string_scores(W.float(), nf, lab, nl, contexts.NextStateTable(graph.table))
+    return cpu.string_scores(W, nf, lab, nl, self.context)
+
+  def _hypotheses(self, batch_dims, B, labels, num_labels, device, what='labels'):
+    labels, num_labels = torch.as_tensor(labels), torch.as_tensor(num_labels)
+    if labels.ndim != len(batch_dims) + 2 or tuple(labels.shape[:-2]) != batch_dims:
+      raise ValueError(f'{what} should be [batch..., N, U] with batch dims {batch_dims}, got '
+                       f'{tuple(labels.shape)}')
+    N, U = labels.shape[-2:]
+    if N < 1:
+      raise ValueError(f'{what} holds no hypothesis (N = 0)')
+    if tuple(num_labels.shape) != (*batch_dims, N):
+      raise ValueError(f'num_{what} should be {(*batch_dims, N)}, got {tuple(num_labels.shape)}')
+    return (labels.to(device=device, dtype=torch.int64).reshape(B, N, U),
+            num_labels.to(device=device, dtype=torch.int64).reshape(B, N))
+
+  def string_weights(self, frames: torch.Tensor, num_frames: torch.Tensor, labels: torch.Tensor,
+                     num_labels: torch.Tensor, cache: Optional[T] = None) -> torch.Tensor:
+    """The Log weights [batch..., N] of N label strings per utterance (not in
+    the reference): entry n is _string_forward(..., Log) of labels[..., n, :] /
+    num_labels[..., n] on the utterance's arc weights, which are computed and
+    read once for all N -- what rescores the list `beam_search` returns. The
+    definition is include/lt_strings.h: labels outside 1..V are epsilons, a
+    num_labels outside [0, U] (so -1 marks an empty slot) or a string with no
+    path scores -inf, num_frames = 0 with num_labels = 0 scores 0. Weights are
+    not normalised: subtract _forward's log_z for log-probabilities.
+
+    Differentiable w.r.t. the weight function: the gradient of entry n is
+    that hypothesis' arc occupancies; a -inf entry has a zero gradient. ROCm
+    tensors run lt_table_strings_forward / lt_table_strings_backward (one
+    launch each; the gradient is deterministic); past their range (N > 64,
+    U > 255, or, when a gradient is wanted, a frame of more than 20320
+    weights) and on the host, the restatement in torch ops
+    (cpu.string_scores). FrameDependent with any context that has a
+    next-state table; FrameLabelDependent raises NotImplementedError.
+    """
+    if not isinstance(self.alignment, alignments.FrameDependent):
+      raise NotImplementedError('string_weights implements FrameDependent alignments, got '
+                                f'{type(self.alignment).__name__}')
+    W, nf, batch_dims, B, _, _, _ = self._prepare(cache, frames, num_frames)
+    lab, nl = self._hypotheses(batch_dims, B, labels, num_labels, W.device)
+    weights = self._string_weights(W, nf, lab, nl)
+    return self._home(weights.reshape(*batch_dims, lab.shape[1]), frames)
+
+  def nbest_risk(self, frames: torch.Tensor, num_frames: torch.Tensor, labels: torch.Tensor,
+                 num_labels: torch.Tensor, hyp_labels: torch.Tensor,
+                 hyp_num_labels: torch.Tensor, costs: Optional[torch.Tensor] = None,
+                 cache: Optional[T] = None):
+    """N-best minimum-risk training (MWER over an N-best list; not in the
+    reference): with w_n = string_weights of hypothesis n,
+      p_n = softmax_n(w_n) over the hypotheses of finite weight, risk = sum_n p_n c_n.
+    Returns (risk [batch...], costs [batch..., N] float32, posteriors
+    [batch..., N]). The default cost is last_torch_amd.edit_distance of each
+    hypothesis (its first hyp_num_labels labels) against labels / num_labels,
+    as float32; a `costs` tensor [batch..., N] replaces it. Gradients flow
+    into the weight function through string_weights only. An utterance with
+    no hypothesis of finite weight has risk 0 and posteriors 0.
+
+    hyp_labels [batch..., N, U] / hyp_num_labels [batch..., N] take
+    `beam_search`'s labels[..., :U] and num_labels. beam_search marks a slot it
+    could not fill by its score (-inf), with all-zero labels and length 0 --
+    which here is the empty string, a real hypothesis: mask such slots with
+    hyp_num_labels = -1, which is scored -inf and drops out. Duplicate
+    hypotheses each count. One arc_weights call.
+    """
+    if not isinstance(self.alignment, alignments.FrameDependent):
+      raise NotImplementedError('nbest_risk implements FrameDependent alignments, got '
+                                f'{type(self.alignment).__name__}')
+    W, nf, batch_dims, B, _, _, _ = self._prepare(cache, frames, num_frames)
+    hyp, hnl = self._hypotheses(batch_dims, B, hyp_labels, hyp_num_labels, W.device, 'hyp_labels')
+    N, U = hyp.shape[1:]
+    with torch.no_grad():
+      if costs is None:
+        kept = torch.arange(U, device=W.device) < hnl[:, :, None]
+        costs = risk_lib.edit_distance(
+            torch.where(kept, hyp, torch.zeros_like(hyp)).reshape(*batch_dims, N, U), None,
+            torch.as_tensor(labels).to(W.device), torch.as_tensor(num_labels).to(W.device))
+      costs = torch.as_tensor(costs).detach().to(device=W.device, dtype=torch.float32)
+      if tuple(costs.shape) != (*batch_dims, N):
+        raise ValueError(f'costs should be {(*batch_dims, N)}, got {tuple(costs.shape)}')
+      costs = costs.reshape(B, N)
+    w = self._string_weights(W, nf, hyp, hnl).float()
+    fin = torch.isfinite(w.detach())
+    safe = torch.where(fin, w, torch.zeros_like(w))
+    top = torch.where(fin, safe, torch.full_like(w, -torch.inf)).detach().amax(dim=-1, keepdim=True)
+    top = torch.where(torch.isfinite(top), top, torch.zeros_like(top))
+    e = torch.where(fin, torch.exp(safe - top), torch.zeros_like(w))
+    post = e / e.sum(dim=-1, keepdim=True).clamp_min(torch.finfo(torch.float32).tiny)
+    risk = (post * costs).sum(dim=-1)
+    return (self._home(risk.reshape(batch_dims), frames),
+            self._home(costs.reshape(*batch_dims, N), frames),
+            self._home(post.reshape(*batch_dims, N), frames))
 
   @staticmethod
   def _align_dense(graph, W, nf, lab, nl):
