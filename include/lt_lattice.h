@@ -502,5 +502,7 @@ const char* lt_version(void);
 #include "lt_beam.h"
 /* N label strings per utterance on shared weights, with the gradient, likewise. */
 #include "lt_strings.h"
+/* Prefix beam search with the joint weight function fused in, likewise. */
+#include "lt_beam_joint.h"
 
 #endif /* LT_LATTICE_H_ */

@@ -104,6 +104,10 @@ _SIG = {
     'lt_table_beam_search_workspace_bytes': [_G, _TP, _I32, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_beam_search': [_G, _TP, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P,
                              ctypes.c_size_t, _P],
+    'lt_joint_beam_search_workspace_bytes': [_G, _TP, ctypes.POINTER(JointParams), _I32,
+                                             ctypes.POINTER(ctypes.c_size_t)],
+    'lt_joint_beam_search': [_G, _TP, ctypes.POINTER(JointParams), _P, _I32, _I32, _P, _P, _P, _P,
+                             _P, _P, ctypes.c_size_t, _P],
     'lt_table_strings_workspace_bytes': [_G, _TP, _I32, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_strings_forward': [_G, _TP, _P, _P, _I32, _P, _P, _P, _P, ctypes.c_size_t, _I32, _P],
     'lt_table_strings_backward': [_G, _TP, _P, _P, _I32, _P, _P, _P, _P, _P, _P, ctypes.c_size_t,
@@ -143,7 +147,8 @@ _SIG = {
 # string's alignments, the string scatter), include/lt_paths.h (scoring given
 # paths, the path scatter, edit distance), include/lt_beam.h (prefix beam
 # search), include/lt_strings.h (N label strings per utterance on shared
-# weights) and include/lt_lattice.h (everything else)
+# weights), include/lt_beam_joint.h (beam search with the joint weight function
+# fused in) and include/lt_lattice.h (everything else)
 EXPORTED_ALIGN = ('lt_table_align_workspace_bytes', 'lt_table_align')
 EXPORTED_SAMPLE = ('lt_table_sample_workspace_bytes', 'lt_table_sample')
 EXPORTED_EXPECT = ('lt_table_expectation_workspace_bytes', 'lt_table_expectation')
@@ -154,10 +159,11 @@ EXPORTED_PATHS = ('lt_table_path_score', 'lt_table_path_scatter', 'lt_edit_dista
 EXPORTED_BEAM = ('lt_table_beam_search_workspace_bytes', 'lt_table_beam_search')
 EXPORTED_STRINGS = ('lt_table_strings_workspace_bytes', 'lt_table_strings_forward',
                     'lt_table_strings_backward')
+EXPORTED_BEAM_JOINT = ('lt_joint_beam_search_workspace_bytes', 'lt_joint_beam_search')
 EXPORTED = (tuple(n for n in _SIG
                   if n not in (EXPORTED_ALIGN + EXPORTED_SAMPLE + EXPORTED_EXPECT +
                                EXPORTED_POSTERIOR + EXPORTED_ALIGN_EXPECT + EXPORTED_PATHS +
-                               EXPORTED_BEAM + EXPORTED_STRINGS)) +
+                               EXPORTED_BEAM + EXPORTED_STRINGS + EXPORTED_BEAM_JOINT)) +
             ('lt_last_error', 'lt_version'))
 
 
@@ -1210,3 +1216,54 @@ def loss_grad_joint(ctx_proj, frame_proj, out_weight, out_bias, num_frames, labe
                                   _ptr(workspace), workspace.numel(), _stream()),
          'lt_loss_grad_joint')
   return loss, log_z, num, dpc, dpf.reshape(B, T, H), dwo, dbias
+
+
+# ---------------------------------------------------------------------------
+# Beam search with the joint weight function fused in (lt_beam_joint.hip)
+# ---------------------------------------------------------------------------
+def joint_beam_search_supported(graph, batch, frames, hidden, beam_size, precision='fp32'):
+  """Whether lt_joint_beam_search takes this problem (FrameDependent,
+  beam_size <= 64, V + 1 <= 64, hidden a multiple of 16 up to 1024 whose LDS
+  image fits the CU): a host-only query, no launch. Other errors raise."""
+  pb = TableProblem(batch, frames, 0, LT_DTYPE_F32)
+  jp = JointParams(hidden, JOINT_SPLIT if precision == 'fp32' else JOINT_BF16, None, None, None,
+                   None)
+  return _supported('lt_joint_beam_search_workspace_bytes', graph, pb, ctypes.byref(jp),
+                    int(beam_size), ctypes.byref(ctypes.c_size_t(0)))
+
+
+def joint_beam_search(graph, ctx_proj, frame_proj, out_weight, out_bias, num_frames, beam_size,
+                      semiring, precision='fp32', want_trace=False):
+  """lt_joint_beam_search: table_beam_search on joint_weights(...)'s fp32 W
+  without W in memory -- the beam's rows are formed on the matrix cores inside
+  the search. ctx_proj [C, H], frame_proj [B, T, H], out_weight [V+1, H],
+  out_bias [V+1] (fp32). Returns what table_beam_search returns."""
+  if frame_proj.ndim != 3:
+    raise ValueError(f'frame_proj must be [B, T, H], got {tuple(frame_proj.shape)}')
+  B, T, H = frame_proj.shape
+  if tuple(ctx_proj.shape) != (graph.C, H) or tuple(out_weight.shape) != (graph.V + 1, H):
+    raise ValueError(f'projections {tuple(ctx_proj.shape)}, {tuple(out_weight.shape)} do not match '
+                     f'the graph (C={graph.C}, V+1={graph.V + 1}) and H={H}')
+  jp, ops = _joint(ctx_proj, frame_proj, out_weight, out_bias, precision)
+  pb = TableProblem(B, T, 0, LT_DTYPE_F32)
+  K = int(beam_size)
+  dev = frame_proj.device
+  nbytes, ws = _workspace('lt_joint_beam_search_workspace_bytes', graph, pb, frame_proj,
+                          ctypes.byref(jp), K, alloc=False)
+  if want_trace:
+    nbytes -= 4 * B * T * K   # the backpointers go to the caller's trace
+  ws = torch.empty([(nbytes + 15) // 16 * 4], dtype=torch.float32, device=dev)
+  labels = torch.empty([B, K, T], dtype=torch.int64, device=dev)
+  num_labels = torch.empty([B, K], dtype=torch.int32, device=dev)
+  scores = _f32([B, K], frame_proj)
+  trace = step = None
+  if want_trace:
+    trace = torch.empty([B, T, K], dtype=torch.int32, device=dev)
+    step = _f32([B, T, K], frame_proj)
+  _check(lib().lt_joint_beam_search(ctypes.byref(graph.g), ctypes.byref(pb), ctypes.byref(jp),
+                                    _ptr(num_frames), K, semiring, _ptr(labels), _ptr(num_labels),
+                                    _ptr(scores), _ptr(trace), _ptr(step), _ptr(ws),
+                                    ws.numel() * 4, _stream()), 'lt_joint_beam_search')
+  del ops
+  out = (labels, num_labels, scores)
+  return out + (trace, step) if want_trace else out

@@ -882,7 +882,11 @@ class RecognitionLattice(nn.Module, Generic[T]):
     that has a next-state table; FrameLabelDependent raises
     NotImplementedError. ROCm tensors run lt_table_beam_search (one launch);
     past its range (beam_size > 64, V > 1023) and on the host, the same
-    definition in torch ops (cpu.beam_search).
+    definition in torch ops (cpu.beam_search). A JointWeightFn on a ROCm
+    device can instead form the arc weights inside the search
+    (lt_joint_beam_search, the same beams bit for bit while the projections
+    stay within +-40): its lattice_fusion setting decides, and 'auto' does so
+    exactly where the arc weights would not fit in memory.
     """
     if not isinstance(self.alignment, alignments.FrameDependent):
       raise NotImplementedError('beam_search implements FrameDependent alignments, got '
@@ -892,6 +896,9 @@ class RecognitionLattice(nn.Module, Generic[T]):
       raise ValueError(f'beam_size should be >= 1, but got {beam_size}')
     if getattr(semiring, 'name', None) not in ('Log', 'MaxTropical'):
       raise NotImplementedError(f'beam_search supports Log and MaxTropical, got {semiring!r}')
+    fused = self._fused_joint_beam(cache, frames, num_frames, K, semiring)
+    if fused is not None:
+      return fused
     W, nf, batch_dims, B, _, _, _ = self._prepare(cache, frames, num_frames)
     with torch.no_grad():
       W = W.detach()
@@ -909,6 +916,28 @@ class RecognitionLattice(nn.Module, Generic[T]):
     return (self._home(labels.reshape(*batch_dims, K, Tn), frames),
             self._home(num_labels.long().reshape(*batch_dims, K), frames),
             self._home(scores.reshape(*batch_dims, K), frames))
+
+  def _fused_joint_beam(self, cache, frames, num_frames, K, semiring):
+    """beam_search through JointWeightFn.fused_beam_search (lt_joint_beam_search)
+    when the weight function takes that path on a ROCm device; else None."""
+    fn = getattr(self.weight_fn, 'fused_beam_search', None)
+    batch_dims = tuple(num_frames.shape)
+    if (fn is None or not frames.is_cuda or frames.ndim < 3 or
+        tuple(frames.shape[:-2]) != batch_dims):
+      return None
+    if cache is None:
+      cache = self.weight_fn_cacher()
+    B = 1
+    for d in batch_dims:
+      B *= d
+    Tn = frames.shape[-2]
+    out = fn(cache, frames.reshape(B, Tn, frames.shape[-1]), _lengths(num_frames, B, frames.device),
+             self._graph(frames.device), K, _semiring_id(semiring))
+    if out is None:
+      return None
+    labels, num_labels, scores = out
+    return (labels.reshape(*batch_dims, K, Tn), num_labels.long().reshape(*batch_dims, K),
+            scores.reshape(*batch_dims, K))
 
   def _path_weights(self, W, nf, paths):
     """path weights [B, S] of paths [B, S, T] over prepared W / nf,

@@ -165,7 +165,10 @@ class JointWeightFn(WeightFn[torch.Tensor]):
   (lt_loss_grad_joint: W and dW never in HBM) instead of materialising W.
   'auto' takes it where it measured faster than the separate launches
   (``fused_lattice_preferred``), 'on' whenever the shape allows it, 'off'
-  never."""
+  never. ``RecognitionLattice.beam_search`` reads the same setting for the
+  fused joint beam search (lt_joint_beam_search: only the beam's rows of W
+  are formed, inside the search): 'on' whenever the shape allows it, 'off'
+  never, 'auto' by ``fused_beam_preferred``."""
 
   def __init__(self, vocab_size: int, hidden_size: int, device=None, fused: bool = True,
                backward_chunk: int = 16384, precision: str = 'fp32',
@@ -228,6 +231,29 @@ class JointWeightFn(WeightFn[torch.Tensor]):
     bias = torch.cat([self.to_blank.bias, self.to_vocab.bias], 0)
     return _JointLossFn.apply(pc, pf, wo, bias, num_frames, labels, num_labels, self.precision)
 
+  def fused_beam_search(self, cache, frames, num_frames, graph, beam_size, semiring_id):
+    """RecognitionLattice.beam_search's (labels, num_labels, scores) with the
+    arc weights formed inside the search (lt_joint_beam_search) for frames
+    [B, T, F], or None where this weight function does not take that path
+    (lattice_fusion, device, shape)."""
+    from last_torch_amd import _native
+    if self.lattice_fusion == 'off' or not self._use_kernel(frames) or frames.ndim != 3:
+      return None
+    B, T = frames.shape[:2]
+    if not _native.joint_beam_search_supported(graph, B, T, self.hidden_size, beam_size,
+                                               self.precision):
+      return None
+    if self.lattice_fusion == 'auto' and not fused_beam_preferred(
+        B, T, graph.C, graph.V + 1, self.hidden_size, frames.device):
+      return None
+    with torch.no_grad():
+      pc = self.context_projection(cache)
+      pf = self.frame_projection(frames)
+      wo = torch.cat([self.to_blank.weight, self.to_vocab.weight], 0)
+      bias = torch.cat([self.to_blank.bias, self.to_vocab.bias], 0)
+      return _native.joint_beam_search(graph, pc, pf, wo, bias, num_frames, beam_size,
+                                       semiring_id, self.precision)
+
   def forward(self, cache, frame, state=None):
     ctx = cache
     if state is None and self._use_kernel(frame):
@@ -254,6 +280,23 @@ def fused_lattice_preferred(batch, frames, labels, hidden):
   separate launches."""
   del batch, frames, labels, hidden
   return False
+
+
+def fused_beam_preferred(batch, frames, states, out_dim, hidden, device):
+  """Where 'auto' takes the fused joint beam search (lt_joint_beam_search)
+  instead of lt_joint_weights_ex + lt_table_beam_search: where the fp32 W
+  [B, T, C, V+1] plus the producer's workspace would not fit in half of the
+  device memory that is free now. That call could only fail before (a trigram
+  over 32 labels at B = 64, T = 1000 is 8.9 GB of W, a 4-gram 286 GB), so this
+  adds a capability and changes nothing that worked. Everywhere else 'auto'
+  keeps the materialised path. profiles/beam_joint_bench.jsonl has the two
+  side by side at B = 64, T = 1000, V = 32: the bigram (C = 33) is 1.03-2.6x
+  slower fused, the trigram (C = 1,057) 0.39-0.79x. That argues for widening
+  the rule to large C at large B T, but the crossover between the two and its
+  dependence on B T are not measured, so the rule is not widened."""
+  need = 4 * batch * frames * states * out_dim + 256 + 4 * hidden * (states + batch * frames)
+  free, _ = torch.cuda.mem_get_info(device)
+  return need > free // 2
 
 
 class SharedEmbCacher(WeightFnCacher[torch.Tensor]):
