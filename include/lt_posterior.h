@@ -50,7 +50,9 @@ extern "C" {
  * max_frames rows of 64 * ceil((U+1)/64) positions (rounded up to 64, 128 or
  * 256) fit 160 KiB beside the prologue's arrays, else in `workspace`
  * (lt_table_align_posteriors_workspace_bytes() bytes, 8-byte aligned; 0 when
- * unused, then it may be NULL). in_offsets / in_arcs of *g are not read. */
+ * unused, then it may be NULL). in_offsets / in_arcs of *g are not read.
+ * Label strings of 256 <= max_labels <= 1023: lt_table_align_posteriors_long
+ * (lt_posterior_long.h, included below). */
 int lt_table_align_posteriors_workspace_bytes(const lt_graph* g, const lt_table_problem* pb,
                                               size_t* bytes);
 int lt_table_align_posteriors(const lt_graph* g, const lt_table_problem* pb, const void* W,
@@ -62,5 +64,7 @@ int lt_table_align_posteriors(const lt_graph* g, const lt_table_problem* pb, con
 #ifdef __cplusplus
 }
 #endif
+
+#include "lt_posterior_long.h"
 
 #endif /* LT_POSTERIOR_H_ */

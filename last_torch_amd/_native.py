@@ -95,6 +95,8 @@ _SIG = {
     'lt_table_align': [_G, _TP] + [_P] * 8 + [ctypes.c_size_t, _P],
     'lt_table_align_posteriors_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_align_posteriors': [_G, _TP] + [_P] * 7 + [ctypes.c_size_t, _P],
+    'lt_table_align_posteriors_long_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
+    'lt_table_align_posteriors_long': [_G, _TP] + [_P] * 7 + [ctypes.c_size_t, _P],
     'lt_table_align_expectation_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_align_expectation': [_G, _TP] + [_P] * 13 + [ctypes.c_size_t, _P],
     'lt_table_string_scatter': [_G, _TP] + [_P] * 7,
@@ -153,6 +155,8 @@ EXPORTED_ALIGN = ('lt_table_align_workspace_bytes', 'lt_table_align')
 EXPORTED_SAMPLE = ('lt_table_sample_workspace_bytes', 'lt_table_sample')
 EXPORTED_EXPECT = ('lt_table_expectation_workspace_bytes', 'lt_table_expectation')
 EXPORTED_POSTERIOR = ('lt_table_align_posteriors_workspace_bytes', 'lt_table_align_posteriors')
+EXPORTED_POSTERIOR_LONG = ('lt_table_align_posteriors_long_workspace_bytes',
+                           'lt_table_align_posteriors_long')
 EXPORTED_ALIGN_EXPECT = ('lt_table_align_expectation_workspace_bytes',
                          'lt_table_align_expectation', 'lt_table_string_scatter')
 EXPORTED_PATHS = ('lt_table_path_score', 'lt_table_path_scatter', 'lt_edit_distance')
@@ -162,7 +166,8 @@ EXPORTED_STRINGS = ('lt_table_strings_workspace_bytes', 'lt_table_strings_forwar
 EXPORTED_BEAM_JOINT = ('lt_joint_beam_search_workspace_bytes', 'lt_joint_beam_search')
 EXPORTED = (tuple(n for n in _SIG
                   if n not in (EXPORTED_ALIGN + EXPORTED_SAMPLE + EXPORTED_EXPECT +
-                               EXPORTED_POSTERIOR + EXPORTED_ALIGN_EXPECT + EXPORTED_PATHS +
+                               EXPORTED_POSTERIOR + EXPORTED_POSTERIOR_LONG +
+                               EXPORTED_ALIGN_EXPECT + EXPORTED_PATHS +
                                EXPORTED_BEAM + EXPORTED_STRINGS + EXPORTED_BEAM_JOINT)) +
             ('lt_last_error', 'lt_version'))
 
@@ -720,6 +725,32 @@ def table_align_posteriors(graph, W, num_frames, labels, num_labels):
                                          _ptr(num_frames), _ptr(labels), _ptr(num_labels),
                                          _ptr(emission), _ptr(log_prob), _ptr(ws), nbytes,
                                          _stream()), 'lt_table_align_posteriors')
+  return emission, log_prob
+
+
+def table_align_posteriors_long_supported(graph, W, labels):
+  """Whether lt_table_align_posteriors_long takes this problem (FrameDependent,
+  256 <= U <= 1023): a host-only query, no launch. Other errors raise."""
+  pb = _tproblem(graph, W, labels.shape[-1])
+  return _supported('lt_table_align_posteriors_long_workspace_bytes', graph, pb,
+                    ctypes.byref(ctypes.c_size_t(0)))
+
+
+def table_align_posteriors_long(graph, W, num_frames, labels, num_labels):
+  """lt_table_align_posteriors_long: table_align_posteriors for label strings
+  of 256 <= U <= 1023, one launch. Returns (emission fp32 [B, T, U], log_prob
+  fp32 [B]); raises LatticeLibraryError (LT_EUNSUPPORTED) for
+  FrameLabelDependent graphs or outside that range."""
+  pb = _tproblem(graph, W, labels.shape[-1])
+  B, T = W.shape[:2]
+  U = labels.shape[-1]
+  nbytes, ws = _workspace('lt_table_align_posteriors_long_workspace_bytes', graph, pb, W)
+  emission = _f32([B, T, U], W)
+  log_prob = _f32([B], W)
+  _check(lib().lt_table_align_posteriors_long(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W),
+                                              _ptr(num_frames), _ptr(labels), _ptr(num_labels),
+                                              _ptr(emission), _ptr(log_prob), _ptr(ws), nbytes,
+                                              _stream()), 'lt_table_align_posteriors_long')
   return emission, log_prob
 
 

@@ -62,11 +62,12 @@ struct StringLds {
 // weight offsets of its positions (ob: the blank arc, ol: the lexical arc),
 // and a last barrier after which the table's image is dead and the region may
 // be overwritten. A: kernel arguments with labels, table, U, C, V, R,
-// stage_tab. lt_align.hip and lt_align_post.hip call it.
-template <int P, int NT, int MID, typename A>
+// stage_tab. lt_align.hip and lt_align_post.hip call it. lt_align_post_long.hip
+// splits SP = 256 NW positions over NW waves a direction: a lane's positions
+// then start at pos0 + lane*P, pos0 the first position of its wave.
+template <int P, int NT, int MID, int SP = 64 * P, typename A>
 LT_DEVINL StringLds string_prologue(const A& a, int b, int tid, int lane, unsigned char* sm,
-                                    int (&ob)[P], int (&ol)[P]) {
-  constexpr int SP = 64 * P;
+                                    int (&ob)[P], int (&ol)[P], int pos0 = 0) {
   StringLds s;
   s.ctx = (int*)sm;
   s.yn = s.ctx + SP;
@@ -99,8 +100,8 @@ LT_DEVINL StringLds string_prologue(const A& a, int b, int tid, int lane, unsign
   __syncthreads();
 #pragma unroll
   for (int j = 0; j < P; ++j) {
-    ob[j] = s.ctx[lane * P + j];
-    ol[j] = ob[j] + s.yn[lane * P + j];
+    ob[j] = s.ctx[pos0 + lane * P + j];
+    ol[j] = ob[j] + s.yn[pos0 + lane * P + j];
   }
   __syncthreads();  // the table's image is dead: the region may be overwritten
   return s;

@@ -19,7 +19,17 @@ under load settles first, as bench.py does), then the median over BATCHES (7)
 event-timed batches of REPS (10) calls; the three kernels alternate batch by
 batch. The restatement takes a fraction of a second per call: one warm-up,
 then the median of RESTATE_CALLS (3) single calls.
-ONLY=bench|bf16 runs one workload.
+ONLY=bench|bf16|long runs one workload.
+
+The long leg (lt_table_align_posteriors_long, lt_align_post_long.hip) times,
+at B = 64, T = 1000, V = 32 bigram and U = 300 / 600 / 1000 in fp32 and bf16,
+  align_post_long_ms   _native.table_align_posteriors_long
+  short_u255_ms        _native.table_align_posteriors at U = 255 on the same
+                       weights, batch by batch in turn with it: the per-frame
+                       cost of the one-wave recursion in the same session
+  restatement_ms       cpu.align_posteriors on the device at the same U: what
+                       align_posteriors ran for these shapes before
+and appends each line to profiles/align_post_long_bench.jsonl as well.
 """
 import json
 import os
@@ -81,6 +91,51 @@ def run(name, V, n, B, T, U, dtype=torch.float32):
       'device': torch.cuda.get_device_name(0)}), flush=True)
 
 
+def run_long(B, T, U, dtype):
+  V = 32
+  table = contexts.FullNGram(vocab_size=V, context_size=1).next_state_table().to(torch.int32)
+  C = table.shape[0]
+  g = torch.Generator(device='cuda')
+  g.manual_seed(0)
+  W = torch.randn([B, T, C, V + 1], generator=g, device='cuda').to(dtype)
+  nf = torch.full([B], T, dtype=torch.int32, device='cuda')
+  lab = torch.randint(1, V + 1, (B, U), generator=g, device='cuda', dtype=torch.int32)
+  nl = torch.full([B], U, dtype=torch.int32, device='cuda')
+  lab_s, nl_s = lab[:, :255].contiguous(), torch.full_like(nl, 255)
+  graph = nat.TableGraph(table, 0, 'cuda')
+  ctx = contexts.NextStateTable(graph.table)
+
+  def long():
+    return nat.table_align_posteriors_long(graph, W, nf, lab, nl)
+
+  def short():
+    return nat.table_align_posteriors(graph, W, nf, lab_s, nl_s)
+
+  def restate():
+    return cpu.align_posteriors(W, nf.long(), lab, nl.long(), ctx, alignments.FrameDependent())
+
+  nbytes = nat.ctypes.c_size_t(0)
+  pb = nat._tproblem(graph, W, U)
+  nat._check(nat.lib().lt_table_align_posteriors_long_workspace_bytes(
+      nat.ctypes.byref(graph.g), nat.ctypes.byref(pb), nat.ctypes.byref(nbytes)), 'query')
+  diff = float((long()[0] - restate()[0]).abs().max())
+  (l_ms, s_ms), spread = medians([long, short])
+  r = sorted(batch_ms(restate, 1) for _ in range(RESTATE_CALLS))
+  line = json.dumps({
+      'workload': 'long strings, FrameDependent x FullNGram bigram V=32', 'B': B, 'T': T, 'U': U,
+      'C': int(C), 'V': V, 'dtype': str(dtype).split('.')[-1], 'align_post_long_ms': l_ms,
+      'short_u255_ms': s_ms, 'restatement_ms': statistics.median(r),
+      'restatement_over_long': statistics.median(r) / l_ms, 'long_over_short_u255': l_ms / s_ms,
+      'long_us_per_frame': 1e3 * l_ms / T, 'short_u255_us_per_frame': 1e3 * s_ms / T,
+      'align_post_long_min_max_ms': spread[0], 'short_u255_min_max_ms': spread[1],
+      'restatement_min_max_ms': (r[0], r[-1]), 'workspace_bytes': nbytes.value,
+      'max_abs_diff': diff, 'batches': BATCHES, 'reps': REPS, 'settle_s': SETTLE_S,
+      'device': torch.cuda.get_device_name(0)})
+  print(line, flush=True)
+  with open(os.path.join(ROOT, 'profiles', 'align_post_long_bench.jsonl'), 'a') as f:
+    f.write(line + '\n')
+
+
 def main():
   if not torch.cuda.is_available():
     raise SystemExit('align_post_bench.py needs a ROCm GPU')
@@ -89,6 +144,10 @@ def main():
     run('FrameDependent x FullNGram bigram V=32 (bench shape)', 32, 1, 64, 1000, 100)
   if only in (None, 'bf16'):
     run('the bench shape, bf16 W', 32, 1, 64, 1000, 100, torch.bfloat16)
+  if only in (None, 'long'):
+    for U in (300, 600, 1000):
+      for dtype in (torch.float32, torch.bfloat16):
+        run_long(64, 1000, U, dtype)
 
 
 if __name__ == '__main__':
