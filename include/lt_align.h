@@ -44,7 +44,9 @@ extern "C" {
  * terms (one bit, or ceil(log2(K+1)) bits, per frame and position) stay in
  * LDS while max_frames of them fit 160 KiB, else in `workspace`
  * (lt_table_align_workspace_bytes() bytes, 8-byte aligned; 0 when unused,
- * then it may be NULL). in_offsets / in_arcs of *g are not read. */
+ * then it may be NULL). in_offsets / in_arcs of *g are not read.
+ * FrameDependent strings of 256 .. 4095 labels: lt_table_align_long
+ * (lt_align_long.h, included below). */
 int lt_table_align_workspace_bytes(const lt_graph* g, const lt_table_problem* pb, size_t* bytes);
 int lt_table_align(const lt_graph* g, const lt_table_problem* pb, const void* W,
                    const int32_t* num_frames, const int32_t* labels, const int32_t* num_labels,
@@ -54,5 +56,7 @@ int lt_table_align(const lt_graph* g, const lt_table_problem* pb, const void* W,
 #ifdef __cplusplus
 }
 #endif
+
+#include "lt_align_long.h"
 
 #endif /* LT_ALIGN_H_ */

@@ -93,6 +93,8 @@ _SIG = {
     'lt_table_viterbi': [_G, _TP, _P, _P, _I32, _P, _P, _P, ctypes.c_size_t, _P],
     'lt_table_align_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_align': [_G, _TP] + [_P] * 8 + [ctypes.c_size_t, _P],
+    'lt_table_align_long_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
+    'lt_table_align_long': [_G, _TP] + [_P] * 8 + [ctypes.c_size_t, _P],
     'lt_table_align_posteriors_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_align_posteriors': [_G, _TP] + [_P] * 7 + [ctypes.c_size_t, _P],
     'lt_table_align_posteriors_long_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
@@ -143,7 +145,7 @@ _SIG = {
                    _P],
 }
 # the functions each header of the C ABI declares: include/lt_align.h (forced
-# alignment), include/lt_sample.h (path sampling), include/lt_expect.h
+# alignment), include/lt_align_long.h (of long label strings), include/lt_sample.h (path sampling), include/lt_expect.h
 # (posterior means of arc values), include/lt_posterior.h (emission posteriors
 # of a label string), include/lt_string_expect.h (expected values over a label
 # string's alignments, the string scatter), include/lt_paths.h (scoring given
@@ -152,6 +154,7 @@ _SIG = {
 # weights), include/lt_beam_joint.h (beam search with the joint weight function
 # fused in) and include/lt_lattice.h (everything else)
 EXPORTED_ALIGN = ('lt_table_align_workspace_bytes', 'lt_table_align')
+EXPORTED_ALIGN_LONG = ('lt_table_align_long_workspace_bytes', 'lt_table_align_long')
 EXPORTED_SAMPLE = ('lt_table_sample_workspace_bytes', 'lt_table_sample')
 EXPORTED_EXPECT = ('lt_table_expectation_workspace_bytes', 'lt_table_expectation')
 EXPORTED_POSTERIOR = ('lt_table_align_posteriors_workspace_bytes', 'lt_table_align_posteriors')
@@ -165,7 +168,7 @@ EXPORTED_STRINGS = ('lt_table_strings_workspace_bytes', 'lt_table_strings_forwar
                     'lt_table_strings_backward')
 EXPORTED_BEAM_JOINT = ('lt_joint_beam_search_workspace_bytes', 'lt_joint_beam_search')
 EXPORTED = (tuple(n for n in _SIG
-                  if n not in (EXPORTED_ALIGN + EXPORTED_SAMPLE + EXPORTED_EXPECT +
+                  if n not in (EXPORTED_ALIGN + EXPORTED_ALIGN_LONG + EXPORTED_SAMPLE + EXPORTED_EXPECT +
                                EXPORTED_POSTERIOR + EXPORTED_POSTERIOR_LONG +
                                EXPORTED_ALIGN_EXPECT + EXPORTED_PATHS +
                                EXPORTED_BEAM + EXPORTED_STRINGS + EXPORTED_BEAM_JOINT)) +
@@ -699,6 +702,33 @@ def table_align(graph, W, num_frames, labels, num_labels):
   _check(lib().lt_table_align(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W), _ptr(num_frames),
                               _ptr(labels), _ptr(num_labels), _ptr(out), _ptr(frames),
                               _ptr(weight), _ptr(ws), nbytes, _stream()), 'lt_table_align')
+  return out, frames, weight
+
+
+def table_align_long_supported(graph, W, labels):
+  """Whether lt_table_align_long takes this problem (FrameDependent,
+  256 <= U <= 4095): a host-only query, no launch. Other errors raise."""
+  pb = _tproblem(graph, W, labels.shape[-1])
+  return _supported('lt_table_align_long_workspace_bytes', graph, pb,
+                    ctypes.byref(ctypes.c_size_t(0)))
+
+
+def table_align_long(graph, W, num_frames, labels, num_labels):
+  """lt_table_align_long: table_align for label strings of 256 <= U <= 4095,
+  one launch. Returns (alignment_labels int64 [B, T], label_frames int64
+  [B, U], path weights [B]); raises LatticeLibraryError (LT_EUNSUPPORTED) for
+  FrameLabelDependent graphs or outside that range."""
+  pb = _tproblem(graph, W, labels.shape[-1])
+  B, T = W.shape[:2]
+  U = labels.shape[-1]
+  nbytes, ws = _workspace('lt_table_align_long_workspace_bytes', graph, pb, W)
+  out = torch.empty([B, T], dtype=torch.int64, device=W.device)
+  frames = torch.empty([B, U], dtype=torch.int64, device=W.device)
+  weight = _f32([B], W)
+  _check(lib().lt_table_align_long(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W),
+                                   _ptr(num_frames), _ptr(labels), _ptr(num_labels), _ptr(out),
+                                   _ptr(frames), _ptr(weight), _ptr(ws), nbytes, _stream()),
+         'lt_table_align_long')
   return out, frames, weight
 
 

@@ -16,8 +16,9 @@ weights once through the ``WeightFn`` plugin as a contiguous
   _string_forward -> lt_num_forward; autograd: lt_loss_backward (Log) /
                      lt_table_num_backward (MaxTropical, Real)
   shortest_path   -> lt_viterbi
-  align           -> lt_table_align (forced alignment; not in the reference);
-                     past its range lt_table_num_backward (Max) compacted
+  align           -> lt_table_align (forced alignment; not in the reference),
+                     from U = 256 to 4095 lt_table_align_long; past their
+                     range lt_table_num_backward (Max) compacted
   align_posteriors -> lt_table_align_posteriors (emission posteriors of the
                      label string; not in the reference), from U = 256 to 1023
                      lt_table_align_posteriors_long; past their range the
@@ -637,6 +638,12 @@ class RecognitionLattice(nn.Module, Generic[T]):
     path_weights equals _string_forward(..., MaxTropical) bit for bit. An
     utterance of weight -inf (no path, -inf arcs, num_labels outside [0, U])
     is unaligned: all 0 / all -1.
+
+    ROCm tensors run one launch of lt_table_align (U <= 255, K <= 15) or of
+    lt_table_align_long (FrameDependent, 256 <= U <= 4095); FrameLabelDependent
+    beyond K = 15 or U = 255, and U > 4095, take the dense string gradient
+    (_align_dense), which raises where its own kernel refuses the labels (its
+    LDS ends near U = 1900). The three routes give the same answer.
     """
     batch_dims = tuple(num_frames.shape)
     if tuple(frames.shape[:-2]) != batch_dims:
@@ -657,10 +664,13 @@ class RecognitionLattice(nn.Module, Generic[T]):
         out = cpu.align(W, nf, lab, nl.long(), self.context, self.alignment)
       else:
         graph = self._graph(W.device)
-        # one launch (lt_table_align); past its range (U > 255, K > 15) the
-        # dense string gradient, compacted
+        # one launch: lt_table_align (U <= 255, K <= 15), lt_table_align_long
+        # (FrameDependent, 256 <= U <= 4095); past both (FrameLabelDependent
+        # beyond K = 15 or U = 255, U > 4095) the dense string gradient, compacted
         if _native.table_align_supported(graph, W, lab):
           out = _native.table_align(graph, W, nf, lab, nl)
+        elif _native.table_align_long_supported(graph, W, lab):
+          out = _native.table_align_long(graph, W, nf, lab, nl)
         else:
           out = self._align_dense(graph, W, nf, lab, nl)
     alignment_labels, label_frames, weights = out

@@ -16,6 +16,13 @@ Each timing: untimed calls for SETTLE_S seconds (default 1.0; the clock under
 load settles first, as bench.py does), then the median over BATCHES (7)
 event-timed batches of REPS (10) calls. The routes alternate batch by batch.
 ONLY=bench|bf16|t2000|fld2 runs one workload.
+
+ONLY=long times lt_table_align_long (lt_align_long.hip, 256 <= U <= 4095) the
+same way: B = 64, V = 32 bigram, fp32 and bf16, (T, U) = (1000, 300),
+(1000, 1000), (2100, 2000), (4200, 4000); each point against _align_dense on
+the same tensors (null where the dense route refuses the shape: its string
+gradient keeps 68 bytes of LDS a label) and against lt_table_align at (1000,
+255) in the same session, per frame.
 """
 import json
 import os
@@ -65,10 +72,60 @@ def run(name, V, n, K, B, T, U, dtype=torch.float32):
       'device': torch.cuda.get_device_name(0)}), flush=True)
 
 
+def _problem(V, B, T, U, dtype):
+  table = contexts.FullNGram(vocab_size=V, context_size=1).next_state_table().to(torch.int32)
+  g = torch.Generator(device='cuda')
+  g.manual_seed(0)
+  W = torch.randn([B, T, table.shape[0], V + 1], generator=g, device='cuda').to(dtype)
+  nf = torch.full([B], T, dtype=torch.int32, device='cuda')
+  lab = torch.randint(1, V + 1, (B, U), generator=g, device='cuda', dtype=torch.int32)
+  nl = torch.full([B], U, dtype=torch.int32, device='cuda')
+  return nat.TableGraph(table, 0, 'cuda'), W, nf, lab, nl
+
+
+def run_long(dtype, points, V=32, B=64):
+  short_args = _problem(V, B, 1000, 255, dtype)
+  (short_ms,), (short_spread,) = medians([lambda: nat.table_align(*short_args)])
+  del short_args
+  for T, U in points:
+    args = _problem(V, B, T, U, dtype)
+
+    def long():
+      return nat.table_align_long(*args)
+
+    def dense():
+      return RecognitionLattice._align_dense(*args)
+
+    try:
+      equal = all(bool(torch.equal(x, y)) for x, y in zip(long(), dense()))
+      (l_ms, d_ms), (l_spread, d_spread) = medians([long, dense])
+    except nat.LatticeLibraryError as e:  # the dense route refuses the shape
+      equal, d_ms, d_spread, refusal = None, None, None, str(e)
+      (l_ms,), (l_spread,) = medians([long])
+    else:
+      refusal = None
+    print(json.dumps({
+        'workload': 'lt_table_align_long, FullNGram bigram', 'B': B, 'T': T, 'U': U,
+        'NW': (U + 256) // 256, 'V': V, 'dtype': str(dtype).split('.')[-1], 'align_long_ms': l_ms,
+        'dense_route_ms': d_ms, 'dense_over_long': d_ms / l_ms if d_ms else None,
+        'dense_route_refusal': refusal, 'align_long_min_max_ms': l_spread,
+        'dense_min_max_ms': d_spread, 'outputs_equal': equal, 'short_u255_t1000_ms': short_ms,
+        'short_min_max_ms': short_spread, 'us_per_frame': 1e3 * l_ms / T,
+        'short_us_per_frame': short_ms, 'per_frame_over_short': (l_ms / T) / (short_ms / 1000),
+        'batches': BATCHES, 'reps': REPS, 'settle_s': SETTLE_S,
+        'device': torch.cuda.get_device_name(0)}), flush=True)
+    del args
+
+
 def main():
   if not torch.cuda.is_available():
     raise SystemExit('align_bench.py needs a ROCm GPU')
   only = os.environ.get('ONLY')
+  if only == 'long':
+    points = [(1000, 300), (1000, 1000), (2100, 2000), (4200, 4000)]
+    run_long(torch.float32, points)
+    run_long(torch.bfloat16, points)
+    return
   if only in (None, 'bench'):
     run('FrameDependent x FullNGram bigram V=32 (bench shape)', 32, 1, 0, 64, 1000, 100)
   if only in (None, 'bf16'):
