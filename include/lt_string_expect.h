@@ -124,4 +124,6 @@ int lt_table_string_scatter(const lt_graph* g, const lt_table_problem* pb,
 }
 #endif
 
+#include "lt_string_expect_long.h"
+
 #endif /* LT_STRING_EXPECT_H_ */

@@ -102,6 +102,9 @@ _SIG = {
     'lt_table_align_expectation_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_align_expectation': [_G, _TP] + [_P] * 13 + [ctypes.c_size_t, _P],
     'lt_table_string_scatter': [_G, _TP] + [_P] * 7,
+    'lt_table_align_expectation_long_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
+    'lt_table_align_expectation_long': [_G, _TP] + [_P] * 13 + [ctypes.c_size_t, _P],
+    'lt_table_string_scatter_long': [_G, _TP] + [_P] * 7,
     'lt_table_sample_workspace_bytes': [_G, _TP, _I32, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_sample': [_G, _TP, _P, _P, _P, _P, _I32, ctypes.c_uint64, _P, _P, _P,
                         ctypes.c_size_t, _P],
@@ -148,7 +151,8 @@ _SIG = {
 # alignment), include/lt_align_long.h (of long label strings), include/lt_sample.h (path sampling), include/lt_expect.h
 # (posterior means of arc values), include/lt_posterior.h (emission posteriors
 # of a label string), include/lt_string_expect.h (expected values over a label
-# string's alignments, the string scatter), include/lt_paths.h (scoring given
+# string's alignments, the string scatter), include/lt_string_expect_long.h
+# (both for long label strings), include/lt_paths.h (scoring given
 # paths, the path scatter, edit distance), include/lt_beam.h (prefix beam
 # search), include/lt_strings.h (N label strings per utterance on shared
 # weights), include/lt_beam_joint.h (beam search with the joint weight function
@@ -162,6 +166,8 @@ EXPORTED_POSTERIOR_LONG = ('lt_table_align_posteriors_long_workspace_bytes',
                            'lt_table_align_posteriors_long')
 EXPORTED_ALIGN_EXPECT = ('lt_table_align_expectation_workspace_bytes',
                          'lt_table_align_expectation', 'lt_table_string_scatter')
+EXPORTED_ALIGN_EXPECT_LONG = ('lt_table_align_expectation_long_workspace_bytes',
+                              'lt_table_align_expectation_long', 'lt_table_string_scatter_long')
 EXPORTED_PATHS = ('lt_table_path_score', 'lt_table_path_scatter', 'lt_edit_distance')
 EXPORTED_BEAM = ('lt_table_beam_search_workspace_bytes', 'lt_table_beam_search')
 EXPORTED_STRINGS = ('lt_table_strings_workspace_bytes', 'lt_table_strings_forward',
@@ -170,7 +176,7 @@ EXPORTED_BEAM_JOINT = ('lt_joint_beam_search_workspace_bytes', 'lt_joint_beam_se
 EXPORTED = (tuple(n for n in _SIG
                   if n not in (EXPORTED_ALIGN + EXPORTED_ALIGN_LONG + EXPORTED_SAMPLE + EXPORTED_EXPECT +
                                EXPORTED_POSTERIOR + EXPORTED_POSTERIOR_LONG +
-                               EXPORTED_ALIGN_EXPECT + EXPORTED_PATHS +
+                               EXPORTED_ALIGN_EXPECT + EXPORTED_ALIGN_EXPECT_LONG + EXPORTED_PATHS +
                                EXPORTED_BEAM + EXPORTED_STRINGS + EXPORTED_BEAM_JOINT)) +
             ('lt_last_error', 'lt_version'))
 
@@ -794,7 +800,8 @@ def table_align_expectation_supported(graph, W, labels):
 
 
 def table_align_expectation(graph, W, lexical_values, blank_values, num_frames, labels,
-                            num_labels, want_post=True, want_cov=True):
+                            num_labels, want_post=True, want_cov=True,
+                            entry='lt_table_align_expectation'):
   """lt_table_align_expectation, one launch: (expected [B], log_prob [B],
   emission [B,T,U], blank_occ [B,T,U+1], cov_lex [B,T,U], cov_blank [B,T,U+1])
   for values in string coordinates (lexical_values [B,T,U], blank_values
@@ -802,7 +809,8 @@ def table_align_expectation(graph, W, lexical_values, blank_values, num_frames, 
   values = d log_prob / d string weights) are None without want_post, the
   covariances (d expected / d string weights) without want_cov; neither wanted
   is the value-only call. Raises LatticeLibraryError (LT_EUNSUPPORTED) for
-  FrameLabelDependent graphs or past U = 255."""
+  FrameLabelDependent graphs or past U = 255. `entry`: the ABI call of that
+  signature to make (table_align_expectation_long passes its own)."""
   pb = _tproblem(graph, W, labels.shape[-1])
   B, T = W.shape[:2]
   U = labels.shape[-1]
@@ -812,25 +820,26 @@ def table_align_expectation(graph, W, lexical_values, blank_values, num_frames, 
                      f'[{B}, {T}, {U + 1}]')
   lexical_values = lexical_values.to(device=W.device, dtype=torch.float32).contiguous()
   blank_values = blank_values.to(device=W.device, dtype=torch.float32).contiguous()
-  nbytes, ws = _workspace('lt_table_align_expectation_workspace_bytes', graph, pb, W,
-                          alloc=want_post or want_cov)
+  nbytes, ws = _workspace(entry + '_workspace_bytes', graph, pb, W, alloc=want_post or want_cov)
   expected, log_prob = _f32([B], W), _f32([B], W)
   emission = _f32([B, T, U], W) if want_post else None
   blank_occ = _f32([B, T, U + 1], W) if want_post else None
   cov_lex = _f32([B, T, U], W) if want_cov else None
   cov_blank = _f32([B, T, U + 1], W) if want_cov else None
-  _check(lib().lt_table_align_expectation(
+  _check(getattr(lib(), entry)(
       ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W), _ptr(lexical_values), _ptr(blank_values),
       _ptr(num_frames), _ptr(labels), _ptr(num_labels), _ptr(expected), _ptr(log_prob),
       _ptr(emission), _ptr(blank_occ), _ptr(cov_lex), _ptr(cov_blank), _ptr(ws),
-      nbytes if ws is not None else 0, _stream()), 'lt_table_align_expectation')
+      nbytes if ws is not None else 0, _stream()), entry)
   return expected, log_prob, emission, blank_occ, cov_lex, cov_blank
 
 
-def table_string_scatter(graph, W, g_lex, g_blank, num_frames, labels, num_labels):
+def table_string_scatter(graph, W, g_lex, g_blank, num_frames, labels, num_labels,
+                         entry='lt_table_string_scatter'):
   """lt_table_string_scatter: the dense fp32 dW [B,T,C,V+1] (W's shape) of
   string-coordinate gradients g_lex [B,T,U] / g_blank [B,T,U+1]: the memset and
-  one kernel, positions that share a cell summed in a fixed order."""
+  one kernel, positions that share a cell summed in a fixed order. `entry`: the
+  ABI call of that signature to make (table_string_scatter_long passes its own)."""
   pb = _tproblem(graph, W, labels.shape[-1])
   B, T = W.shape[:2]
   U = labels.shape[-1]
@@ -840,11 +849,37 @@ def table_string_scatter(graph, W, g_lex, g_blank, num_frames, labels, num_label
   g_lex = g_lex.to(device=W.device, dtype=torch.float32).contiguous()
   g_blank = g_blank.to(device=W.device, dtype=torch.float32).contiguous()
   dW = _f32(tuple(W.shape), W)
-  _check(lib().lt_table_string_scatter(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(g_lex),
-                                       _ptr(g_blank), _ptr(num_frames), _ptr(labels),
-                                       _ptr(num_labels), _ptr(dW), _stream()),
-         'lt_table_string_scatter')
+  _check(getattr(lib(), entry)(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(g_lex),
+                               _ptr(g_blank), _ptr(num_frames), _ptr(labels), _ptr(num_labels),
+                               _ptr(dW), _stream()), entry)
   return dW
+
+
+def table_align_expectation_long_supported(graph, W, labels):
+  """Whether lt_table_align_expectation_long (and lt_table_string_scatter_long)
+  takes this problem (FrameDependent, 256 <= U <= 1023): a host-only query, no
+  launch. Other errors raise."""
+  pb = _tproblem(graph, W, labels.shape[-1])
+  return _supported('lt_table_align_expectation_long_workspace_bytes', graph, pb,
+                    ctypes.byref(ctypes.c_size_t(0)))
+
+
+def table_align_expectation_long(graph, W, lexical_values, blank_values, num_frames, labels,
+                                 num_labels, want_post=True, want_cov=True):
+  """lt_table_align_expectation_long: table_align_expectation for label strings
+  of 256 <= U <= 1023, one launch, the same returns and the same want_post /
+  want_cov contract; raises LatticeLibraryError (LT_EUNSUPPORTED) for
+  FrameLabelDependent graphs or outside that range."""
+  return table_align_expectation(graph, W, lexical_values, blank_values, num_frames, labels,
+                                 num_labels, want_post, want_cov,
+                                 entry='lt_table_align_expectation_long')
+
+
+def table_string_scatter_long(graph, W, g_lex, g_blank, num_frames, labels, num_labels):
+  """lt_table_string_scatter_long: table_string_scatter for label strings of
+  256 <= U <= 1023, one kernel."""
+  return table_string_scatter(graph, W, g_lex, g_blank, num_frames, labels, num_labels,
+                              entry='lt_table_string_scatter_long')
 
 
 def table_sample(graph, W, num_frames, log_z, alpha, num_samples, seed):

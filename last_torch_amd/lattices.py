@@ -26,8 +26,10 @@ weights once through the ``WeightFn`` plugin as a contiguous
   align_expectation -> lt_table_align_expectation (expected value of a path
                      quantity over the transcript's alignments, with the
                      posteriors and covariances its backward needs; not in the
-                     reference) + lt_table_string_scatter in the backward; past
-                     its range cpu.align_expectation on the device
+                     reference) + lt_table_string_scatter in the backward, from
+                     U = 256 to 1023 lt_table_align_expectation_long +
+                     lt_table_string_scatter_long; past their range
+                     cpu.align_expectation on the device
   sample          -> lt_den_forward / lt_table_forward (Log) + lt_table_sample
                      (paths from the posterior; not in the reference)
   beam_search     -> lt_table_beam_search (the N best label sequences by
@@ -301,14 +303,20 @@ class _AlignExpectFn(torch.autograd.Function):
   log_prob / d string weights, the covariances = d expected / d string
   weights); the backward combines them with the incoming gradients in string
   coordinates and ONE lt_table_string_scatter call makes the dense dW. A
-  second backward (retain_graph) recomputes them. Not twice differentiable."""
+  second backward (retain_graph) recomputes them. Not twice differentiable.
+  `calls` is the pair of _native bindings to use: SHORT_CALLS (U <= 255) or
+  LONG_CALLS (lt_table_align_expectation_long / lt_table_string_scatter_long,
+  256 <= U <= 1023)."""
+
+  SHORT_CALLS = (_native.table_align_expectation, _native.table_string_scatter)
+  LONG_CALLS = (_native.table_align_expectation_long, _native.table_string_scatter_long)
 
   @staticmethod
-  def forward(ctx, W, lv, bv, nf, lab, nl, graph):
+  def forward(ctx, W, lv, bv, nf, lab, nl, graph, calls=SHORT_CALLS):
     need_w, need_l, need_b = ctx.needs_input_grad[:3]
-    expected, log_prob, *grads = _native.table_align_expectation(
+    expected, log_prob, *grads = calls[0](
         graph, W, lv, bv, nf, lab, nl, want_post=need_w or need_l or need_b, want_cov=need_w)
-    ctx.graph, ctx.grads = graph, grads
+    ctx.graph, ctx.grads, ctx.calls = graph, grads, calls
     ctx.save_for_backward(W, lv, bv, nf, lab, nl)
     return expected, log_prob
 
@@ -318,21 +326,19 @@ class _AlignExpectFn(torch.autograd.Function):
     need_w, need_l, need_b = ctx.needs_input_grad[:3]
     grads, ctx.grads = ctx.grads, None
     if grads is None and (need_w or need_l or need_b):  # a second backward through the same graph
-      grads = _native.table_align_expectation(ctx.graph, W, lv, bv, nf, lab, nl, want_post=True,
-                                              want_cov=need_w)[2:]
+      grads = ctx.calls[0](ctx.graph, W, lv, bv, nf, lab, nl, want_post=True, want_cov=need_w)[2:]
     emission, blank_occ, cov_lex, cov_blank = grads if grads is not None else [None] * 4
     g_e = g_e.float()[:, None, None]
     dW = dl = db = None
     if need_w:
       g_lp = g_lp.float()[:, None, None]
-      dW = _native.table_string_scatter(ctx.graph, W, g_e * cov_lex + g_lp * emission,
-                                        g_e * cov_blank + g_lp * blank_occ, nf, lab,
-                                        nl).to(W.dtype)
+      dW = ctx.calls[1](ctx.graph, W, g_e * cov_lex + g_lp * emission,
+                        g_e * cov_blank + g_lp * blank_occ, nf, lab, nl).to(W.dtype)
     if need_l:
       dl = (g_e * emission).to(lv.dtype)
     if need_b:
       db = (g_e * blank_occ).to(bv.dtype)
-    return dW, dl, db, None, None, None, None
+    return dW, dl, db, None, None, None, None, None
 
 
 class _PathScoreFn(torch.autograd.Function):
@@ -778,8 +784,10 @@ class RecognitionLattice(nn.Module, Generic[T]):
     lexical_values = emission, d expected / d blank_values = blank_occ. On
     ROCm tensors the gradients come from the forward's one
     lt_table_align_expectation call plus one lt_table_string_scatter call in
-    the backward (FrameDependent, U <= 255, fp32 or bf16 weights) and are not
-    twice differentiable; FrameLabelDependent or longer strings run
+    the backward (FrameDependent, U <= 255, fp32 or bf16 weights), or from
+    lt_table_align_expectation_long and lt_table_string_scatter_long in their
+    place (the same for 256 <= U <= 1023), and are not twice differentiable;
+    FrameLabelDependent or longer strings run
     cpu.align_expectation (plain autograd) on the tensors' own device; CPU
     tensors run it on the host. An arc of weight -inf contributes nothing and
     its value is ignored (NaN or inf there is harmless), as are values on
@@ -820,6 +828,8 @@ class RecognitionLattice(nn.Module, Generic[T]):
       graph = self._graph(W.device)
       if _native.table_align_expectation_supported(graph, W, lab):
         out = _AlignExpectFn.apply(W, lv, bv, nf, lab, nl, graph)
+      elif _native.table_align_expectation_long_supported(graph, W, lab):
+        out = _AlignExpectFn.apply(W, lv, bv, nf, lab, nl, graph, _AlignExpectFn.LONG_CALLS)
       else:
         # the restatement on the device: the walk reads the graph's device copy
         # of the next-state table, nothing visits the host
