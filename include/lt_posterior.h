@@ -52,7 +52,9 @@ extern "C" {
  * (lt_table_align_posteriors_workspace_bytes() bytes, 8-byte aligned; 0 when
  * unused, then it may be NULL). in_offsets / in_arcs of *g are not read.
  * Label strings of 256 <= max_labels <= 1023: lt_table_align_posteriors_long
- * (lt_posterior_long.h, included below). */
+ * (lt_posterior_long.h, included below). FrameLabelDependent graphs
+ * (1 <= expansions <= 15): lt_table_align_posteriors_fld (lt_posterior_fld.h,
+ * included below). */
 int lt_table_align_posteriors_workspace_bytes(const lt_graph* g, const lt_table_problem* pb,
                                               size_t* bytes);
 int lt_table_align_posteriors(const lt_graph* g, const lt_table_problem* pb, const void* W,
@@ -66,5 +68,6 @@ int lt_table_align_posteriors(const lt_graph* g, const lt_table_problem* pb, con
 #endif
 
 #include "lt_posterior_long.h"
+#include "lt_posterior_fld.h"
 
 #endif /* LT_POSTERIOR_H_ */

@@ -99,6 +99,8 @@ _SIG = {
     'lt_table_align_posteriors': [_G, _TP] + [_P] * 7 + [ctypes.c_size_t, _P],
     'lt_table_align_posteriors_long_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_align_posteriors_long': [_G, _TP] + [_P] * 7 + [ctypes.c_size_t, _P],
+    'lt_table_align_posteriors_fld_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
+    'lt_table_align_posteriors_fld': [_G, _TP] + [_P] * 7 + [ctypes.c_size_t, _P],
     'lt_table_align_expectation_workspace_bytes': [_G, _TP, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_align_expectation': [_G, _TP] + [_P] * 13 + [ctypes.c_size_t, _P],
     'lt_table_string_scatter': [_G, _TP] + [_P] * 7,
@@ -150,7 +152,8 @@ _SIG = {
 # the functions each header of the C ABI declares: include/lt_align.h (forced
 # alignment), include/lt_align_long.h (of long label strings), include/lt_sample.h (path sampling), include/lt_expect.h
 # (posterior means of arc values), include/lt_posterior.h (emission posteriors
-# of a label string), include/lt_string_expect.h (expected values over a label
+# of a label string), include/lt_posterior_long.h (of long label strings),
+# include/lt_posterior_fld.h (on FrameLabelDependent), include/lt_string_expect.h (expected values over a label
 # string's alignments, the string scatter), include/lt_string_expect_long.h
 # (both for long label strings), include/lt_paths.h (scoring given
 # paths, the path scatter, edit distance), include/lt_beam.h (prefix beam
@@ -164,6 +167,8 @@ EXPORTED_EXPECT = ('lt_table_expectation_workspace_bytes', 'lt_table_expectation
 EXPORTED_POSTERIOR = ('lt_table_align_posteriors_workspace_bytes', 'lt_table_align_posteriors')
 EXPORTED_POSTERIOR_LONG = ('lt_table_align_posteriors_long_workspace_bytes',
                            'lt_table_align_posteriors_long')
+EXPORTED_POSTERIOR_FLD = ('lt_table_align_posteriors_fld_workspace_bytes',
+                          'lt_table_align_posteriors_fld')
 EXPORTED_ALIGN_EXPECT = ('lt_table_align_expectation_workspace_bytes',
                          'lt_table_align_expectation', 'lt_table_string_scatter')
 EXPORTED_ALIGN_EXPECT_LONG = ('lt_table_align_expectation_long_workspace_bytes',
@@ -175,7 +180,7 @@ EXPORTED_STRINGS = ('lt_table_strings_workspace_bytes', 'lt_table_strings_forwar
 EXPORTED_BEAM_JOINT = ('lt_joint_beam_search_workspace_bytes', 'lt_joint_beam_search')
 EXPORTED = (tuple(n for n in _SIG
                   if n not in (EXPORTED_ALIGN + EXPORTED_ALIGN_LONG + EXPORTED_SAMPLE + EXPORTED_EXPECT +
-                               EXPORTED_POSTERIOR + EXPORTED_POSTERIOR_LONG +
+                               EXPORTED_POSTERIOR + EXPORTED_POSTERIOR_LONG + EXPORTED_POSTERIOR_FLD +
                                EXPORTED_ALIGN_EXPECT + EXPORTED_ALIGN_EXPECT_LONG + EXPORTED_PATHS +
                                EXPORTED_BEAM + EXPORTED_STRINGS + EXPORTED_BEAM_JOINT)) +
             ('lt_last_error', 'lt_version'))
@@ -787,6 +792,34 @@ def table_align_posteriors_long(graph, W, num_frames, labels, num_labels):
                                               _ptr(num_frames), _ptr(labels), _ptr(num_labels),
                                               _ptr(emission), _ptr(log_prob), _ptr(ws), nbytes,
                                               _stream()), 'lt_table_align_posteriors_long')
+  return emission, log_prob
+
+
+def table_align_posteriors_fld_supported(graph, W, labels):
+  """Whether lt_table_align_posteriors_fld takes this problem
+  (FrameLabelDependent(K), 1 <= K <= 15, U <= 255): a host-only query, no
+  launch. Other errors raise."""
+  pb = _tproblem(graph, W, labels.shape[-1])
+  return _supported('lt_table_align_posteriors_fld_workspace_bytes', graph, pb,
+                    ctypes.byref(ctypes.c_size_t(0)))
+
+
+def table_align_posteriors_fld(graph, W, num_frames, labels, num_labels):
+  """lt_table_align_posteriors_fld: table_align_posteriors on a
+  FrameLabelDependent(K) graph (a frame's expansion slots summed), one launch.
+  Returns (emission fp32 [B, T, U], log_prob fp32 [B]); raises
+  LatticeLibraryError (LT_EUNSUPPORTED) for FrameDependent graphs, K > 15 or
+  past U = 255."""
+  pb = _tproblem(graph, W, labels.shape[-1])
+  B, T = W.shape[:2]
+  U = labels.shape[-1]
+  nbytes, ws = _workspace('lt_table_align_posteriors_fld_workspace_bytes', graph, pb, W)
+  emission = _f32([B, T, U], W)
+  log_prob = _f32([B], W)
+  _check(lib().lt_table_align_posteriors_fld(ctypes.byref(graph.g), ctypes.byref(pb), _ptr(W),
+                                             _ptr(num_frames), _ptr(labels), _ptr(num_labels),
+                                             _ptr(emission), _ptr(log_prob), _ptr(ws), nbytes,
+                                             _stream()), 'lt_table_align_posteriors_fld')
   return emission, log_prob
 
 

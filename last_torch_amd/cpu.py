@@ -8,7 +8,9 @@ host; a missing HIP library raises). The functions here that also take ROCm
 tensors are align_posteriors, align_expectation, path_weights, beam_search
 and edit_distance, which then run their torch ops on that device:
 RecognitionLattice.align_posteriors, align_expectation, path_weights and
-beam_search and last_torch_amd.edit_distance past their kernels' range.
+beam_search and last_torch_amd.edit_distance past their kernels' range
+(align_posteriors: FrameDependent past U = 1023, FrameLabelDependent(K) with
+K > 15 or past U = 255).
 
 One formulation covers both alignment lattices and any context dependency.
 A frame of FrameDependent (K = 0) or FrameLabelDependent(K) is

@@ -21,7 +21,8 @@ weights once through the ``WeightFn`` plugin as a contiguous
                      range lt_table_num_backward (Max) compacted
   align_posteriors -> lt_table_align_posteriors (emission posteriors of the
                      label string; not in the reference), from U = 256 to 1023
-                     lt_table_align_posteriors_long; past their range the
+                     lt_table_align_posteriors_long, FrameLabelDependent(K <= 15)
+                     lt_table_align_posteriors_fld; past their range the
                      torch restatement (cpu.align_posteriors) on the device
   align_expectation -> lt_table_align_expectation (expected value of a path
                      quantity over the transcript's alignments, with the
@@ -713,10 +714,12 @@ class RecognitionLattice(nn.Module, Generic[T]):
     through either output.
 
     ROCm tensors run one launch of lt_table_align_posteriors (FrameDependent,
-    U <= 255, fp32 or bf16 weights) or of lt_table_align_posteriors_long
-    (the same for 256 <= U <= 1023); FrameLabelDependent or longer strings
-    run the torch restatement (cpu.align_posteriors) on the tensors' own
-    device; CPU tensors run it on the host.
+    U <= 255, fp32 or bf16 weights), of lt_table_align_posteriors_long (the
+    same for 256 <= U <= 1023) or of lt_table_align_posteriors_fld
+    (FrameLabelDependent(K), K <= 15, U <= 255); FrameLabelDependent with
+    K > 15 or U > 255 and longer FrameDependent strings run the torch
+    restatement (cpu.align_posteriors) on the tensors' own device; CPU tensors
+    run it on the host.
     """
     batch_dims = tuple(num_frames.shape)
     if tuple(frames.shape[:-2]) != batch_dims:
@@ -741,6 +744,8 @@ class RecognitionLattice(nn.Module, Generic[T]):
           out = _native.table_align_posteriors(graph, W, nf, lab, nl)
         elif _native.table_align_posteriors_long_supported(graph, W, lab):
           out = _native.table_align_posteriors_long(graph, W, nf, lab, nl)
+        elif _native.table_align_posteriors_fld_supported(graph, W, lab):
+          out = _native.table_align_posteriors_fld(graph, W, nf, lab, nl)
         else:
           # the same restatement on the device: the walk reads the graph's
           # device copy of the next-state table, nothing visits the host

@@ -19,7 +19,7 @@ under load settles first, as bench.py does), then the median over BATCHES (7)
 event-timed batches of REPS (10) calls; the three kernels alternate batch by
 batch. The restatement takes a fraction of a second per call: one warm-up,
 then the median of RESTATE_CALLS (3) single calls.
-ONLY=bench|bf16|long runs one workload.
+ONLY=bench|bf16|long|fld runs one workload.
 
 The long leg (lt_table_align_posteriors_long, lt_align_post_long.hip) times,
 at B = 64, T = 1000, V = 32 bigram and U = 300 / 600 / 1000 in fp32 and bf16,
@@ -30,6 +30,17 @@ at B = 64, T = 1000, V = 32 bigram and U = 300 / 600 / 1000 in fp32 and bf16,
   restatement_ms       cpu.align_posteriors on the device at the same U: what
                        align_posteriors ran for these shapes before
 and appends each line to profiles/align_post_long_bench.jsonl as well.
+
+The fld leg (lt_table_align_posteriors_fld, lt_align_post_fld.hip) times, at
+B = 64, T = 1000, V = 32 bigram, U = 100, FrameLabelDependent(K) for K = 1, 2,
+4, 15 in fp32 and bf16,
+  align_post_fld_ms    _native.table_align_posteriors_fld
+  frame_dependent_ms   _native.table_align_posteriors on the same W and labels
+                       (K = 0), batch by batch in turn with it: the floor for
+                       what a frame can cost
+  restatement_ms       cpu.align_posteriors on the device with the same K: what
+                       align_posteriors ran for FrameLabelDependent before
+and appends each line to profiles/align_post_fld_bench.jsonl as well.
 """
 import json
 import os
@@ -136,6 +147,52 @@ def run_long(B, T, U, dtype):
     f.write(line + '\n')
 
 
+def run_fld(B, T, U, K, dtype):
+  V = 32
+  table = contexts.FullNGram(vocab_size=V, context_size=1).next_state_table().to(torch.int32)
+  C = table.shape[0]
+  g = torch.Generator(device='cuda')
+  g.manual_seed(0)
+  W = torch.randn([B, T, C, V + 1], generator=g, device='cuda').to(dtype)
+  nf = torch.full([B], T, dtype=torch.int32, device='cuda')
+  lab = torch.randint(1, V + 1, (B, U), generator=g, device='cuda', dtype=torch.int32)
+  nl = torch.full([B], U, dtype=torch.int32, device='cuda')
+  graph = nat.TableGraph(table, K, 'cuda')
+  graph0 = nat.TableGraph(table, 0, 'cuda')
+  ctx = contexts.NextStateTable(graph.table)
+
+  def fld():
+    return nat.table_align_posteriors_fld(graph, W, nf, lab, nl)
+
+  def fd():
+    return nat.table_align_posteriors(graph0, W, nf, lab, nl)
+
+  def restate():
+    return cpu.align_posteriors(W, nf.long(), lab, nl.long(), ctx,
+                                alignments.FrameLabelDependent(K))
+
+  nbytes = nat.ctypes.c_size_t(0)
+  pb = nat._tproblem(graph, W, U)
+  nat._check(nat.lib().lt_table_align_posteriors_fld_workspace_bytes(
+      nat.ctypes.byref(graph.g), nat.ctypes.byref(pb), nat.ctypes.byref(nbytes)), 'query')
+  diff = float((fld()[0] - restate()[0]).abs().max())
+  (k_ms, d_ms), spread = medians([fld, fd])
+  r = sorted(batch_ms(restate, 1) for _ in range(RESTATE_CALLS))
+  line = json.dumps({
+      'workload': 'FrameLabelDependent(K) x FullNGram bigram V=32', 'K': K, 'B': B, 'T': T,
+      'U': U, 'C': int(C), 'V': V, 'dtype': str(dtype).split('.')[-1], 'align_post_fld_ms': k_ms,
+      'frame_dependent_ms': d_ms, 'restatement_ms': statistics.median(r),
+      'restatement_over_fld': statistics.median(r) / k_ms, 'fld_over_frame_dependent': k_ms / d_ms,
+      'fld_us_per_frame': 1e3 * k_ms / T, 'frame_dependent_us_per_frame': 1e3 * d_ms / T,
+      'align_post_fld_min_max_ms': spread[0], 'frame_dependent_min_max_ms': spread[1],
+      'restatement_min_max_ms': (r[0], r[-1]), 'workspace_bytes': nbytes.value,
+      'max_abs_diff': diff, 'batches': BATCHES, 'reps': REPS, 'settle_s': SETTLE_S,
+      'device': torch.cuda.get_device_name(0)})
+  print(line, flush=True)
+  with open(os.path.join(ROOT, 'profiles', 'align_post_fld_bench.jsonl'), 'a') as f:
+    f.write(line + '\n')
+
+
 def main():
   if not torch.cuda.is_available():
     raise SystemExit('align_post_bench.py needs a ROCm GPU')
@@ -148,6 +205,10 @@ def main():
     for U in (300, 600, 1000):
       for dtype in (torch.float32, torch.bfloat16):
         run_long(64, 1000, U, dtype)
+  if only in (None, 'fld'):
+    for K in (1, 2, 4, 15):
+      for dtype in (torch.float32, torch.bfloat16):
+        run_fld(64, 1000, 100, K, dtype)
 
 
 if __name__ == '__main__':
