@@ -14,7 +14,7 @@ lg_of = $(subst M1,-1,$(word 1,$(subst _, ,$(1))))
 lgn_of = $(word 1,$(subst _, ,$(1)))
 p_of = $(word 2,$(subst _, ,$(1)))
 LIB := last_torch_amd/liblt_lattice.so
-DEPS := $(CSRC)/lt_kernels.h $(CSRC)/lt_table_common.h $(CSRC)/lt_string_common.h $(CSRC)/lt_beam_common.h $(CSRC)/lt_joint.h include/lt_lattice.h include/lt_align.h include/lt_align_long.h include/lt_sample.h include/lt_expect.h include/lt_posterior.h include/lt_posterior_long.h include/lt_posterior_fld.h include/lt_string_expect.h include/lt_string_expect_long.h include/lt_paths.h include/lt_beam.h include/lt_strings.h include/lt_beam_joint.h
+DEPS := $(CSRC)/lt_kernels.h $(CSRC)/lt_table_common.h $(CSRC)/lt_string_common.h $(CSRC)/lt_beam_common.h $(CSRC)/lt_joint.h include/lt_lattice.h include/lt_align.h include/lt_align_long.h include/lt_sample.h include/lt_expect.h include/lt_posterior.h include/lt_posterior_long.h include/lt_posterior_fld.h include/lt_string_expect.h include/lt_string_expect_long.h include/lt_paths.h include/lt_beam.h include/lt_strings.h include/lt_beam_joint.h include/lt_joint_strings.h
 
 CPULIB := last_torch_amd/liblt_lattice_cpu.so
 CXX ?= g++
@@ -34,16 +34,16 @@ $(OBJ)/%.o: $(CSRC)/%.hip $(DEPS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-# lt_strings.hip, lt_beam_joint.hip, lt_align_post_long.hip, lt_align_expect_long.hip and lt_align_long.hip
+# lt_strings.hip, lt_beam_joint.hip, lt_joint_strings.hip, lt_align_post_long.hip, lt_align_expect_long.hip and lt_align_long.hip
 # are compiled without packed fp32 instructions. lt_align_long.hip: a frame is four independent add pairs a
 # lane, which the compiler may pair into v_pk_add_f32; every sum stays a scalar v_add_f32, as in lt_align.o's
 # code, whose path weights its own must equal bit for bit. lt_align_expect_long.hip: a lane steps four
 # independent positions through lae_mean, whose adds, products and the one fma the compiler may pair into
 # v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32; each position keeps lt_align_expect.o's scalar sequence, so the
 # two kernels round the definition alike.
-$(OBJ)/lt_align_expect_long.o build/diag/lt_align_expect_long.o $(OBJ)/lt_align_post_long.o build/diag/lt_align_post_long.o $(OBJ)/lt_align_long.o build/diag/lt_align_long.o $(OBJ)/lt_strings.o build/diag/lt_strings.o $(OBJ)/lt_beam_joint.o build/diag/lt_beam_joint.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+$(OBJ)/lt_align_expect_long.o build/diag/lt_align_expect_long.o $(OBJ)/lt_align_post_long.o build/diag/lt_align_post_long.o $(OBJ)/lt_align_long.o build/diag/lt_align_long.o $(OBJ)/lt_strings.o build/diag/lt_strings.o $(OBJ)/lt_beam_joint.o build/diag/lt_beam_joint.o $(OBJ)/lt_joint_strings.o build/diag/lt_joint_strings.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
-$(LIB): $(OBJ)/lt_lattice.o $(OBJ)/lt_pipe.o $(OBJ)/lt_chunk.o $(OBJ)/lt_table.o $(OBJ)/lt_align.o $(OBJ)/lt_align_post.o $(OBJ)/lt_align_post_long.o $(OBJ)/lt_align_post_fld.o $(OBJ)/lt_align_long.o $(OBJ)/lt_align_expect.o $(OBJ)/lt_align_expect_long.o $(OBJ)/lt_sample.o $(OBJ)/lt_beam.o $(OBJ)/lt_beam_joint.o $(OBJ)/lt_paths.o $(OBJ)/lt_strings.o $(OBJ)/lt_edit.o $(OBJ)/lt_expect.o $(OBJ)/lt_producer.o $(OBJ)/lt_joint.o $(OBJ)/lt_vit.o $(OBJ)/lt_tri.o $(INST_OBJS)
+$(LIB): $(OBJ)/lt_lattice.o $(OBJ)/lt_pipe.o $(OBJ)/lt_chunk.o $(OBJ)/lt_table.o $(OBJ)/lt_align.o $(OBJ)/lt_align_post.o $(OBJ)/lt_align_post_long.o $(OBJ)/lt_align_post_fld.o $(OBJ)/lt_align_long.o $(OBJ)/lt_align_expect.o $(OBJ)/lt_align_expect_long.o $(OBJ)/lt_sample.o $(OBJ)/lt_beam.o $(OBJ)/lt_beam_joint.o $(OBJ)/lt_joint_strings.o $(OBJ)/lt_paths.o $(OBJ)/lt_strings.o $(OBJ)/lt_edit.o $(OBJ)/lt_expect.o $(OBJ)/lt_producer.o $(OBJ)/lt_joint.o $(OBJ)/lt_vit.o $(OBJ)/lt_tri.o $(INST_OBJS)
 	$(HIPCC) -shared --offload-arch=$(ARCH) -o $@ $^
 
 oracle:
@@ -76,7 +76,7 @@ $(STAMP_OBJ)/lt_tri4.o: $(CSRC)/lt_tri4.hip $(DEPS)
 $(STAMP_OBJ)/lt_tri.o: $(CSRC)/lt_tri.hip $(DEPS)
 	@mkdir -p $(STAMP_OBJ)
 	$(HIPCC) $(HIPFLAGS) -DLT_STAMPS -DLT_DIAG -c -o $@ $<
-stamps: $(STAMP_OBJ)/lt_lattice.o $(STAMP_OBJ)/lt_pipe.o $(OBJ)/lt_chunk.o $(OBJ)/lt_table.o $(OBJ)/lt_align.o $(OBJ)/lt_align_post.o $(OBJ)/lt_align_post_long.o $(OBJ)/lt_align_post_fld.o $(OBJ)/lt_align_long.o $(OBJ)/lt_align_expect.o $(OBJ)/lt_align_expect_long.o $(OBJ)/lt_sample.o $(OBJ)/lt_beam.o $(OBJ)/lt_beam_joint.o $(OBJ)/lt_paths.o $(OBJ)/lt_strings.o $(OBJ)/lt_edit.o $(OBJ)/lt_expect.o $(OBJ)/lt_producer.o $(STAMP_OBJ)/lt_joint.o $(OBJ)/lt_vit.o $(STAMP_OBJ)/lt_tri.o $(STAMP_OBJ)/lt_tri4.o $(foreach v,$(VARIANTS),$(STAMP_OBJ)/lt_inst_$(v).o)
+stamps: $(STAMP_OBJ)/lt_lattice.o $(STAMP_OBJ)/lt_pipe.o $(OBJ)/lt_chunk.o $(OBJ)/lt_table.o $(OBJ)/lt_align.o $(OBJ)/lt_align_post.o $(OBJ)/lt_align_post_long.o $(OBJ)/lt_align_post_fld.o $(OBJ)/lt_align_long.o $(OBJ)/lt_align_expect.o $(OBJ)/lt_align_expect_long.o $(OBJ)/lt_sample.o $(OBJ)/lt_beam.o $(OBJ)/lt_beam_joint.o $(OBJ)/lt_joint_strings.o $(OBJ)/lt_paths.o $(OBJ)/lt_strings.o $(OBJ)/lt_edit.o $(OBJ)/lt_expect.o $(OBJ)/lt_producer.o $(STAMP_OBJ)/lt_joint.o $(OBJ)/lt_vit.o $(STAMP_OBJ)/lt_tri.o $(STAMP_OBJ)/lt_tri4.o $(foreach v,$(VARIANTS),$(STAMP_OBJ)/lt_inst_$(v).o)
 	$(HIPCC) -shared --offload-arch=$(ARCH) -o $(STAMP_OBJ)/liblt_lattice_stamps.so $^
 .PHONY: stamps
 
@@ -89,7 +89,7 @@ $(DIAG_OBJ)/lt_inst_%.o: $(CSRC)/lt_inst.hip $(DEPS)
 $(DIAG_OBJ)/%.o: $(CSRC)/%.hip $(DEPS)
 	@mkdir -p $(DIAG_OBJ)
 	$(HIPCC) $(HIPFLAGS) -DLT_DIAG -c -o $@ $<
-diag: $(DIAG_OBJ)/lt_lattice.o $(DIAG_OBJ)/lt_pipe.o $(DIAG_OBJ)/lt_chunk.o $(DIAG_OBJ)/lt_table.o $(DIAG_OBJ)/lt_align.o $(DIAG_OBJ)/lt_align_post.o $(DIAG_OBJ)/lt_align_post_long.o $(DIAG_OBJ)/lt_align_post_fld.o $(DIAG_OBJ)/lt_align_long.o $(DIAG_OBJ)/lt_align_expect.o $(DIAG_OBJ)/lt_align_expect_long.o $(DIAG_OBJ)/lt_sample.o $(DIAG_OBJ)/lt_beam.o $(DIAG_OBJ)/lt_beam_joint.o $(DIAG_OBJ)/lt_paths.o $(DIAG_OBJ)/lt_strings.o $(DIAG_OBJ)/lt_edit.o $(DIAG_OBJ)/lt_expect.o $(DIAG_OBJ)/lt_producer.o $(DIAG_OBJ)/lt_joint.o $(DIAG_OBJ)/lt_vit.o $(DIAG_OBJ)/lt_tri.o $(DIAG_OBJ)/lt_tri4.o $(foreach v,$(VARIANTS),$(DIAG_OBJ)/lt_inst_$(v).o)
+diag: $(DIAG_OBJ)/lt_lattice.o $(DIAG_OBJ)/lt_pipe.o $(DIAG_OBJ)/lt_chunk.o $(DIAG_OBJ)/lt_table.o $(DIAG_OBJ)/lt_align.o $(DIAG_OBJ)/lt_align_post.o $(DIAG_OBJ)/lt_align_post_long.o $(DIAG_OBJ)/lt_align_post_fld.o $(DIAG_OBJ)/lt_align_long.o $(DIAG_OBJ)/lt_align_expect.o $(DIAG_OBJ)/lt_align_expect_long.o $(DIAG_OBJ)/lt_sample.o $(DIAG_OBJ)/lt_beam.o $(DIAG_OBJ)/lt_beam_joint.o $(DIAG_OBJ)/lt_joint_strings.o $(DIAG_OBJ)/lt_paths.o $(DIAG_OBJ)/lt_strings.o $(DIAG_OBJ)/lt_edit.o $(DIAG_OBJ)/lt_expect.o $(DIAG_OBJ)/lt_producer.o $(DIAG_OBJ)/lt_joint.o $(DIAG_OBJ)/lt_vit.o $(DIAG_OBJ)/lt_tri.o $(DIAG_OBJ)/lt_tri4.o $(foreach v,$(VARIANTS),$(DIAG_OBJ)/lt_inst_$(v).o)
 	$(HIPCC) -shared --offload-arch=$(ARCH) -o $(DIAG_OBJ)/liblt_lattice_diag.so $^
 .PHONY: diag
 

@@ -504,5 +504,7 @@ const char* lt_version(void);
 #include "lt_strings.h"
 /* Prefix beam search with the joint weight function fused in, likewise. */
 #include "lt_beam_joint.h"
+/* The rows of the joint weight function's W that a label string visits, likewise. */
+#include "lt_joint_strings.h"
 
 #endif /* LT_LATTICE_H_ */

@@ -117,6 +117,10 @@ _SIG = {
                                              ctypes.POINTER(ctypes.c_size_t)],
     'lt_joint_beam_search': [_G, _TP, ctypes.POINTER(JointParams), _P, _I32, _I32, _P, _P, _P, _P,
                              _P, _P, ctypes.c_size_t, _P],
+    'lt_joint_string_rows_workspace_bytes': [_G, _TP, ctypes.POINTER(JointParams),
+                                             ctypes.POINTER(ctypes.c_size_t)],
+    'lt_joint_string_rows': [_G, _TP, ctypes.POINTER(JointParams), _P, _P, _P, _P, _P, _P,
+                             ctypes.c_size_t, _P],
     'lt_table_strings_workspace_bytes': [_G, _TP, _I32, ctypes.POINTER(ctypes.c_size_t)],
     'lt_table_strings_forward': [_G, _TP, _P, _P, _I32, _P, _P, _P, _P, ctypes.c_size_t, _I32, _P],
     'lt_table_strings_backward': [_G, _TP, _P, _P, _I32, _P, _P, _P, _P, _P, _P, ctypes.c_size_t,
@@ -159,7 +163,9 @@ _SIG = {
 # paths, the path scatter, edit distance), include/lt_beam.h (prefix beam
 # search), include/lt_strings.h (N label strings per utterance on shared
 # weights), include/lt_beam_joint.h (beam search with the joint weight function
-# fused in) and include/lt_lattice.h (everything else)
+# fused in), include/lt_joint_strings.h (the rows of the joint weight
+# function's W that a label string visits) and include/lt_lattice.h (everything
+# else)
 EXPORTED_ALIGN = ('lt_table_align_workspace_bytes', 'lt_table_align')
 EXPORTED_ALIGN_LONG = ('lt_table_align_long_workspace_bytes', 'lt_table_align_long')
 EXPORTED_SAMPLE = ('lt_table_sample_workspace_bytes', 'lt_table_sample')
@@ -178,11 +184,13 @@ EXPORTED_BEAM = ('lt_table_beam_search_workspace_bytes', 'lt_table_beam_search')
 EXPORTED_STRINGS = ('lt_table_strings_workspace_bytes', 'lt_table_strings_forward',
                     'lt_table_strings_backward')
 EXPORTED_BEAM_JOINT = ('lt_joint_beam_search_workspace_bytes', 'lt_joint_beam_search')
+EXPORTED_JOINT_STRINGS = ('lt_joint_string_rows_workspace_bytes', 'lt_joint_string_rows')
 EXPORTED = (tuple(n for n in _SIG
                   if n not in (EXPORTED_ALIGN + EXPORTED_ALIGN_LONG + EXPORTED_SAMPLE + EXPORTED_EXPECT +
                                EXPORTED_POSTERIOR + EXPORTED_POSTERIOR_LONG + EXPORTED_POSTERIOR_FLD +
                                EXPORTED_ALIGN_EXPECT + EXPORTED_ALIGN_EXPECT_LONG + EXPORTED_PATHS +
-                               EXPORTED_BEAM + EXPORTED_STRINGS + EXPORTED_BEAM_JOINT)) +
+                               EXPORTED_BEAM + EXPORTED_STRINGS + EXPORTED_BEAM_JOINT +
+                               EXPORTED_JOINT_STRINGS)) +
             ('lt_last_error', 'lt_version'))
 
 
@@ -1396,3 +1404,76 @@ def joint_beam_search(graph, ctx_proj, frame_proj, out_weight, out_bias, num_fra
   del ops
   out = (labels, num_labels, scores)
   return out + (trace, step) if want_trace else out
+
+
+# ---------------------------------------------------------------------------
+# The rows of the joint weight function's W that label strings visit
+# (lt_joint_strings.hip)
+# ---------------------------------------------------------------------------
+_chain_graphs = {}
+
+
+def chain_graph(U, V, device):
+  """The chain table of U label slots over V labels as a TableGraph (cached):
+  U + 1 states, next[k, y-1] = min(k + 1, U) for every label y, K = 0. A string
+  kernel is in state k after k non-epsilon labels, which is how
+  joint_string_rows lays its rows out."""
+  key = (int(U), int(V), str(torch.device(device)))
+  if key not in _chain_graphs:
+    nxt = torch.clamp(torch.arange(1, U + 2, dtype=torch.int32), max=U)
+    _chain_graphs[key] = TableGraph(nxt[:, None].expand(U + 1, V), 0, device)
+  return _chain_graphs[key]
+
+
+def _string_rows_problem(B, T, U, hidden, precision, dtype):
+  if precision not in ('fp32', 'bf16'):
+    raise ValueError(f"joint_string_rows: precision must be 'fp32' or 'bf16', got {precision!r}")
+  if dtype not in (torch.float32, torch.bfloat16):
+    raise TypeError(f'joint_string_rows: the rows are float32 or bfloat16, got {dtype}')
+  pb = TableProblem(B, T, U, LT_DTYPE_BF16 if dtype == torch.bfloat16 else LT_DTYPE_F32)
+  jp = JointParams(hidden, JOINT_SPLIT if precision == 'fp32' else JOINT_BF16, None, None, None,
+                   None)
+  return pb, jp
+
+
+def joint_string_rows_supported(graph, B, T, U, hidden, precision='fp32', dtype=torch.float32):
+  """Whether lt_joint_string_rows takes this problem (FrameDependent,
+  1 <= U <= 4095, V + 1 <= 64, hidden a multiple of 16 up to 1024 whose LDS
+  image fits the CU): a host-only query, no launch. Other errors raise."""
+  pb, jp = _string_rows_problem(B, T, U, hidden, precision, dtype)
+  return _supported('lt_joint_string_rows_workspace_bytes', graph, pb, ctypes.byref(jp),
+                    ctypes.byref(ctypes.c_size_t(0)))
+
+
+def joint_string_rows(graph, ctx_proj, frame_proj, out_weight, out_bias, num_frames, labels,
+                      num_labels, precision='fp32', dtype=torch.float32):
+  """lt_joint_string_rows: (Ws [B, T, U+1, V+1] in `dtype`, states int32
+  [B, U+1]). Ws[b, t, k] is joint_weights(...)[b, t, states[b, k]], bit for bit
+  while the projections stay within +-40, for k up to the number of
+  non-epsilon labels of labels[b] and t < num_frames[b]; zeros (states: -1)
+  elsewhere. With chain_graph(U, V) it is what the string kernels read of W.
+  ctx_proj [C, H], frame_proj [B, T, H], out_weight [V+1, H], out_bias [V+1]
+  (fp32), labels int32 [B, U]."""
+  if frame_proj.ndim != 3:
+    raise ValueError(f'frame_proj must be [B, T, H], got {tuple(frame_proj.shape)}')
+  B, T, H = frame_proj.shape
+  if tuple(ctx_proj.shape) != (graph.C, H) or tuple(out_weight.shape) != (graph.V + 1, H):
+    raise ValueError(f'projections {tuple(ctx_proj.shape)}, {tuple(out_weight.shape)} do not match '
+                     f'the graph (C={graph.C}, V+1={graph.V + 1}) and H={H}')
+  if labels.dtype != torch.int32 or tuple(labels.shape[:-1]) != (B,) or not labels.is_contiguous():
+    raise ValueError('labels must be contiguous int32 [B, U]')
+  U = labels.shape[-1]
+  pb, _ = _string_rows_problem(B, T, U, H, precision, dtype)
+  jp, ops = _joint(ctx_proj, frame_proj, out_weight, out_bias, precision)
+  dev = frame_proj.device
+  nbytes, _ = _workspace('lt_joint_string_rows_workspace_bytes', graph, pb, frame_proj,
+                         ctypes.byref(jp), alloc=False)
+  ws = torch.empty([(nbytes + 15) // 16 * 4], dtype=torch.float32, device=dev)
+  Ws = torch.empty([B, T, U + 1, graph.V + 1], dtype=dtype, device=dev)
+  states = torch.empty([B, U + 1], dtype=torch.int32, device=dev)
+  _check(lib().lt_joint_string_rows(ctypes.byref(graph.g), ctypes.byref(pb), ctypes.byref(jp),
+                                    _ptr(num_frames), _ptr(labels), _ptr(num_labels), _ptr(Ws),
+                                    _ptr(states), _ptr(ws), ws.numel() * 4, _stream()),
+         'lt_joint_string_rows')
+  del ops
+  return Ws, states

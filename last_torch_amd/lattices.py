@@ -650,7 +650,12 @@ class RecognitionLattice(nn.Module, Generic[T]):
     lt_table_align_long (FrameDependent, 256 <= U <= 4095); FrameLabelDependent
     beyond K = 15 or U = 255, and U > 4095, take the dense string gradient
     (_align_dense), which raises where its own kernel refuses the labels (its
-    LDS ends near U = 1900). The three routes give the same answer.
+    LDS ends near U = 1900). The three routes give the same answer. A
+    JointWeightFn on a ROCm device can form only the rows of the arc weights
+    that the label strings visit (lt_joint_string_rows) and run the same two
+    kernels on them, the same outputs bit for bit while the projections stay
+    within +-40: its lattice_fusion setting decides, and 'auto' does so exactly
+    where the arc weights would not fit in memory.
     """
     batch_dims = tuple(num_frames.shape)
     if tuple(frames.shape[:-2]) != batch_dims:
@@ -662,6 +667,17 @@ class RecognitionLattice(nn.Module, Generic[T]):
     if tuple(num_labels.shape) != batch_dims:
       raise ValueError('num_labels and num_frames have different batch_dims: '
                        f'{tuple(num_labels.shape)} vs {batch_dims}')
+    fused = self._fused_joint_rows(cache, frames, num_frames, labels, num_labels)
+    if fused is not None:
+      chain, Ws, nf, lab, nl = fused
+      out = None
+      if _native.table_align_supported(chain, Ws, lab):
+        out = _native.table_align(chain, Ws, nf, lab, nl)
+      elif _native.table_align_long_supported(chain, Ws, lab):
+        out = _native.table_align_long(chain, Ws, nf, lab, nl)
+      if out is not None:
+        return (out[0].reshape(*batch_dims, -1), out[1].reshape(*batch_dims, -1),
+                out[2].reshape(batch_dims))
     W, nf, batch_dims, B, _, _, _ = self._prepare(cache, frames, num_frames)
     lab = torch.as_tensor(labels).reshape(B, -1).to(device=W.device, dtype=torch.int32).contiguous()
     nl = _lengths(num_labels, B, W.device)
@@ -719,7 +735,9 @@ class RecognitionLattice(nn.Module, Generic[T]):
     (FrameLabelDependent(K), K <= 15, U <= 255); FrameLabelDependent with
     K > 15 or U > 255 and longer FrameDependent strings run the torch
     restatement (cpu.align_posteriors) on the tensors' own device; CPU tensors
-    run it on the host.
+    run it on the host. A JointWeightFn on a ROCm device can form only the rows
+    of the arc weights that the label strings visit (lt_joint_string_rows) and
+    run the first two kernels on them, as `align` does.
     """
     batch_dims = tuple(num_frames.shape)
     if tuple(frames.shape[:-2]) != batch_dims:
@@ -731,6 +749,17 @@ class RecognitionLattice(nn.Module, Generic[T]):
     if tuple(num_labels.shape) != batch_dims:
       raise ValueError('num_labels and num_frames have different batch_dims: '
                        f'{tuple(num_labels.shape)} vs {batch_dims}')
+    fused = self._fused_joint_rows(cache, frames, num_frames, labels, num_labels)
+    if fused is not None:
+      chain, Ws, nf, lab, nl = fused
+      out = None
+      if _native.table_align_posteriors_supported(chain, Ws, lab):
+        out = _native.table_align_posteriors(chain, Ws, nf, lab, nl)
+      elif _native.table_align_posteriors_long_supported(chain, Ws, lab):
+        out = _native.table_align_posteriors_long(chain, Ws, nf, lab, nl)
+      if out is not None:
+        return (out[0].reshape(*batch_dims, Ws.shape[1], lab.shape[-1]),
+                out[1].reshape(batch_dims))
     W, nf, batch_dims, B, _, _, _ = self._prepare(cache, frames, num_frames)
     lab = torch.as_tensor(labels).reshape(B, -1).to(device=W.device, dtype=torch.int32).contiguous()
     nl = _lengths(num_labels, B, W.device)
@@ -945,6 +974,27 @@ class RecognitionLattice(nn.Module, Generic[T]):
     return (self._home(labels.reshape(*batch_dims, K, Tn), frames),
             self._home(num_labels.long().reshape(*batch_dims, K), frames),
             self._home(scores.reshape(*batch_dims, K), frames))
+
+  def _fused_joint_rows(self, cache, frames, num_frames, labels, num_labels):
+    """(chain graph, Ws, num_frames, labels, num_labels) for the string kernels
+    through JointWeightFn.fused_string_rows (lt_joint_string_rows: only the
+    rows of the arc weights that the label strings visit) when the weight
+    function takes that path on a ROCm device; else None."""
+    fn = getattr(self.weight_fn, 'fused_string_rows', None)
+    if (fn is None or not frames.is_cuda or frames.ndim < 3 or
+        not isinstance(self.alignment, alignments.FrameDependent)):
+      return None
+    if cache is None:
+      cache = self.weight_fn_cacher()
+    dev = frames.device
+    B = 1
+    for d in num_frames.shape:
+      B *= d
+    nf = _lengths(num_frames, B, dev)
+    lab = torch.as_tensor(labels).reshape(B, -1).to(device=dev, dtype=torch.int32).contiguous()
+    nl = _lengths(num_labels, B, dev)
+    out = fn(cache, frames.reshape(B, *frames.shape[-2:]), nf, lab, nl, self._graph(dev))
+    return None if out is None else (*out, nf, lab, nl)
 
   def _fused_joint_beam(self, cache, frames, num_frames, K, semiring):
     """beam_search through JointWeightFn.fused_beam_search (lt_joint_beam_search)

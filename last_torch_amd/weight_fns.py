@@ -168,7 +168,12 @@ class JointWeightFn(WeightFn[torch.Tensor]):
   never. ``RecognitionLattice.beam_search`` reads the same setting for the
   fused joint beam search (lt_joint_beam_search: only the beam's rows of W
   are formed, inside the search): 'on' whenever the shape allows it, 'off'
-  never, 'auto' by ``fused_beam_preferred``."""
+  never, 'auto' by ``fused_beam_preferred``. ``RecognitionLattice.align`` and
+  ``align_posteriors`` read it for the string rows (lt_joint_string_rows: only
+  the rows of W that the label strings visit are formed, B T (U+1) (V+1)
+  values, and the string kernels run on them over a chain graph): 'on'
+  whenever the shape allows it, 'off' never, 'auto' by
+  ``fused_string_rows_preferred``."""
 
   def __init__(self, vocab_size: int, hidden_size: int, device=None, fused: bool = True,
                backward_chunk: int = 16384, precision: str = 'fp32',
@@ -254,6 +259,32 @@ class JointWeightFn(WeightFn[torch.Tensor]):
       return _native.joint_beam_search(graph, pc, pf, wo, bias, num_frames, beam_size,
                                        semiring_id, self.precision)
 
+  def fused_string_rows(self, cache, frames, num_frames, labels, num_labels, graph):
+    """(chain graph, Ws [B, T, U+1, V+1]): the rows of the arc weights that the
+    label strings visit, laid out on the chain table of their U label slots
+    (lt_joint_string_rows), for frames [B, T, F] and int32 labels [B, U] -- what
+    RecognitionLattice.align and align_posteriors hand to their string kernels
+    in place of (graph, W). None where this weight function does not take that
+    path (lattice_fusion, device, shape)."""
+    from last_torch_amd import _native
+    if self.lattice_fusion == 'off' or not self._use_kernel(frames) or frames.ndim != 3:
+      return None
+    B, T = frames.shape[:2]
+    U = labels.shape[-1]
+    if not _native.joint_string_rows_supported(graph, B, T, U, self.hidden_size, self.precision):
+      return None
+    if self.lattice_fusion == 'auto' and not fused_string_rows_preferred(
+        B, T, U, graph.C, graph.V + 1, self.hidden_size, frames.device):
+      return None
+    with torch.no_grad():
+      pc = self.context_projection(cache)
+      pf = self.frame_projection(frames)
+      wo = torch.cat([self.to_blank.weight, self.to_vocab.weight], 0)
+      bias = torch.cat([self.to_blank.bias, self.to_vocab.bias], 0)
+      Ws, _ = _native.joint_string_rows(graph, pc, pf, wo, bias, num_frames, labels, num_labels,
+                                        self.precision)
+    return _native.chain_graph(U, graph.V, frames.device), Ws
+
   def forward(self, cache, frame, state=None):
     ctx = cache
     if state is None and self._use_kernel(frame):
@@ -297,6 +328,23 @@ def fused_beam_preferred(batch, frames, states, out_dim, hidden, device):
   need = 4 * batch * frames * states * out_dim + 256 + 4 * hidden * (states + batch * frames)
   free, _ = torch.cuda.mem_get_info(device)
   return need > free // 2
+
+
+def fused_string_rows_preferred(batch, frames, labels, states, out_dim, hidden, device):
+  """Where 'auto' forms only the rows a label string visits
+  (lt_joint_string_rows) for align / align_posteriors instead of W: exactly
+  where W would not fit in half of the free device memory (fused_beam_preferred's
+  condition, unchanged) and the rows [B, T, U+1, V+1] plus their workspace
+  (the gathered context rows [B, U+1, H] and the walk's states) would. The
+  materialised call could only fail there, so this adds a capability and
+  changes nothing that worked. Whether 'auto' should also take the rows where
+  W fits but C >> U is not decided (profiles/joint_string_rows_bench.jsonl)."""
+  if not fused_beam_preferred(batch, frames, states, out_dim, hidden, device):
+    return False
+  rows = batch * (labels + 1)
+  need = 4 * frames * rows * out_dim + 4 * rows * (hidden + 1) + 8 * batch + 512
+  free, _ = torch.cuda.mem_get_info(device)
+  return need <= free // 2
 
 
 class SharedEmbCacher(WeightFnCacher[torch.Tensor]):
